@@ -12,8 +12,12 @@ once per iteration.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --workload cfg4            # configs[4] shape: 4K frames pushed from host memory, k=8 on cell flow
+    python bench.py --full                     # plus the informational legs below
+    python bench.py --dump-outputs DIR         # plus DIR/<name>.npy: what the last timed step computed
 
-Prints ONE JSON line on rank 0 (metric = Mpixels/s of flow+k-means, whole job), including
+Prints ONE JSON line on rank 0 (metric = Mpixels/s of flow+k-means, whole job).  A plain run sets up, warms up, times the
+steps and prints the line; with --full it also carries (each leg outside the timed region):
+  config       -- flow_only_mpx_s, lloyd_skip_fraction / lloyd_sweeps, pruned_fit_check, labelled_fit_check, shard_step_ms
   roofline     -- the polynomial-expansion kernel (24 B/px algorithmic) timed with HIP events on its own stream over 64
                   distinct resident 1080p images, against the 8 TB/s HBM peak; sub-objects `flow_iter` (the kernel that
                   dominates a step, 56 B/px), `lloyd` (the full label-less Lloyd sweep over the clip's 6.2e8 vectors, 8 B/point,
@@ -67,8 +71,12 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="frame pairs per flow launch sequence (0 = equal batches <= 32)")
     ap.add_argument("--frames", type=int, default=CLIP_FRAMES, help="clip length (default = the named config)")
     ap.add_argument("--engines", type=int, default=2, help="flow engines (HIP streams) fed round-robin")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational legs outside the timed region")
+    ap.add_argument("--full", action="store_true", help="also run the informational legs outside the timed region "
+                                                        "(extras, roofline, cpu_baseline)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras (flow-only rate, fit checks, "
+                                                             "Lloyd roofline, shard step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--workload", choices=("cfg2", "cfg4"), default="cfg2")
     ap.add_argument("--frames4k", type=int, default=1000, help="frames pushed per step of --workload cfg4 (configs[4]: 1000)")
     args = ap.parse_args()
@@ -93,7 +101,9 @@ def main():
         device = int(os.environ["OFC_BENCH_DEVICE"])  # refuses two ranks on one device)
     rank, world, barrier, allreduce_max = dist.init_from_torch_env(device)
     if args.workload == "cfg4":
-        out = bench_cfg4(args, device, rank, world, barrier, allreduce_max)
+        out, outputs = bench_cfg4(args, device, rank, world, barrier, allreduce_max)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         if world > 1 or force_dist:
             barrier()
             dist.finalize()
@@ -150,6 +160,10 @@ def main():
                        "parallelism": "frames sharded x%d, all-reduce of k*(d+1)+1 f64 per Lloyd iteration, transport %s"
                                       % (world, {"rccl": "RCCL", "gloo-host": "gloo (host fallback)", "none": "none (one rank)"}[dist.TRANSPORT])},
         }
+        if args.dump_outputs:
+            # before any informational leg: the fit checks below run the fit again and rewrite the resident labels
+            dump_outputs(args.dump_outputs, clip_outputs(pipe, p0, centers, inertia, n_iter))
+
     def guarded(slot, fn):
         """an informational leg must never cost the headline line that was already measured"""
         try:
@@ -159,14 +173,14 @@ def main():
             traceback.print_exc()
             return {"error": "%s in %s: %s" % (e.__class__.__name__, slot, e)}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         from opticalflowclustering_amd.cluster import prune_stats
         ps = prune_stats(device)
         out["config"]["lloyd_skip_fraction"] = ps["skip_fraction"]
         out["config"]["lloyd_sweeps"] = {"tile_sweeps": ps["tile_sweeps"], "pruned": ps["pruned_sweeps"], "probes": ps["probe_sweeps"],
                                          "what": "label-less Lloyd iterations over 64-sample tiles; a pruned sweep reads only the "
                                                  "tiles whose (u,v) box is not inside one Voronoi cell (skip fraction = tiles not read)"}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # ---- informational legs, outside the timed region ----
         # (1) the flow alone over the same resident clip (the configs[1] shape: many distinct 1080p pairs per launch sequence)
         barrier()
@@ -185,11 +199,11 @@ def main():
             out["config"]["labelled_fit_check"] = guarded("labelled_fit_check", lambda: labelled_fit_check(pipe, centers, n_iter, device))
             lloyd_roof = guarded("roofline.lloyd", lambda: lloyd_roofline(pipe, centers, device))
     pipe.close()
-    if rank == 0 and world == 1 and not args.no_extras and args.frames == CLIP_FRAMES:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.frames == CLIP_FRAMES:
         # (3) what one rank of an 8-GPU run does per step, alone on this GPU (no collective: RCCL refuses two ranks on one
         # device) -- the numbers the >= 6x scaling target is priced on
         out["config"].update(guarded("shard_step_ms", lambda: shard_step_ms(device, args.engines, centers, int(n_iter))))
-    if rank == 0:
+    if rank == 0 and args.full:
         out["roofline"] = guarded("roofline", lambda: kernel_rooflines(device, out["config"].get("flow_only_mpx_s")))
         if world == 1 and not force_dist and not args.no_extras and isinstance(out["roofline"], dict):
             out["roofline"]["lloyd"] = lloyd_roof
@@ -201,6 +215,36 @@ def main():
         dist.finalize()
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+DUMP_PAIRS, DUMP_PIXELS, DUMP_MAX_BYTES = 16, 1 << 17, 64 << 20
+
+
+def clip_outputs(pipe, p0, centers, inertia, n_iter):
+    """what a caller of the timed step receives: the fit's centres, inertia and iteration count, and a fixed sample of the
+    resident per-pixel results (the whole flow field is 5 GB): the same DUMP_PIXELS pixels of DUMP_PAIRS pairs of this
+    rank's pairs, both drawn once from default_rng(0) in sorted order (clip-wide pair index = p0 + local index)"""
+    P = pipe.W * pipe.H
+    rng = np.random.default_rng(0)
+    pairs = np.sort(rng.choice(pipe.n_pairs, min(DUMP_PAIRS, pipe.n_pairs), replace=False))
+    pix = np.sort(rng.choice(P, min(DUMP_PIXELS, P), replace=False))
+    flow = np.empty((len(pairs), len(pix), 2), np.float32)
+    labels = np.empty((len(pairs), len(pix)), np.float32)
+    for i, t in enumerate(pairs):
+        flow[i] = pipe.flows.download((P, 2), np.float32, offset=int(t) * P * 8)[pix]
+        labels[i] = pipe.labels.download((P,), np.uint8, offset=int(t) * P)[pix]
+    return {"centers": np.asarray(centers, np.float64), "inertia": np.float64(inertia), "n_iter": np.float64(n_iter),
+            "flow_sample": flow, "labels_sample": labels}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64, at most DUMP_MAX_BYTES in all"""
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {n: a.dtype for n, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kernel_rooflines(device, flow_only_mpx_s):
@@ -512,6 +556,8 @@ def bench_cfg4(args, device, rank=0, world=1, barrier=lambda: None, allreduce_ma
     fs.close()
     buf.free()
     from opticalflowclustering_amd import dist
+    outputs = {"cells": np.asarray(cells, np.float32), "centers": np.asarray(centers, np.float64),
+               "inertia": np.float64(inertia), "n_iter": np.float64(n_iter)}
     return {"metric": "Mpixels/s dense flow+kmeans @4K stream", "value": args.steps * (n - 1) * W4 * H4 / 1e6 / dt,
             "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": max(args.warmup, 1),
             "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -521,7 +567,7 @@ def bench_cfg4(args, device, rank=0, world=1, barrier=lambda: None, allreduce_ma
                        "width": W4, "height": H4, "frames": n, "pairs": n - 1, "k": 8, "lloyd_iters": int(n_iter),
                        "cell_vectors": int((n - 1) * 350), "ms_per_frame": 1e3 * dt / args.steps / n,
                        "upload_bytes_per_frame": W4 * H4, "centers": [[float(v) for v in row] for row in centers],
-                       "inertia": float(inertia), "transport": dist.TRANSPORT}}
+                       "inertia": float(inertia), "transport": dist.TRANSPORT}}, outputs
 
 
 if __name__ == "__main__":

@@ -473,7 +473,7 @@ def test_bench_distributed_path_end_to_end_on_one_gpu():
     """bench.py's N > 1 code path in a fresh process under torch.distributed.run with a world-1 RCCL communicator
     (OFC_FORCE_DIST=1): rendezvous over gloo, ofc_dist_init, the send != recv all-reduce of the Lloyd totals on the
     library's stream, dist.finalize -- must give the centres and iteration count of the plain run"""
-    common = ["--gpus", "1", "--frames", "9", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras"]
+    common = ["--gpus", "1", "--frames", "9", "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--no-extras"]
     plain = _run_bench(["bench.py"] + common)
     dist = _run_bench(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                        "--master-port", str(_free_port()), "bench.py"] + common, {"OFC_FORCE_DIST": "1"})
@@ -556,7 +556,7 @@ def test_bench_two_ranks_on_one_gpu_over_the_gloo_transport():
     each owns half of the clip's pairs plus the halo frame, the Lloyd exchange runs over the gloo host transport
     (RCCL refuses two ranks on one device).  Sharding, barriers, max-over-ranks timing, rank-0 JSON, teardown -- and the
     clip-wide fit must equal the one-rank fit over the same clip"""
-    common = ["--frames", "17", "--steps", "1", "--warmup", "1", "--no-cpu"]
+    common = ["--frames", "17", "--steps", "1", "--warmup", "1", "--full", "--no-cpu"]
     plain = _run_bench(["bench.py", "--gpus", "1", "--no-extras"] + common)
     two = _run_bench(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                       "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + common,
@@ -581,6 +581,28 @@ def test_bench_cfg4_one_and_two_ranks():
     assert one["config"]["lloyd_iters"] == two["config"]["lloyd_iters"] >= 2
     assert np.abs(np.array(one["config"]["centers"]) - np.array(two["config"]["centers"])).max() <= 1e-9
     assert abs(one["config"]["inertia"] - two["config"]["inertia"]) <= 1e-9 * one["config"]["inertia"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """a plain bench.py run times its steps and carries none of the --full legs; --dump-outputs writes what the last timed
+    step computed, identical from run to run (no atomics anywhere on the path), with the fit the result line reports"""
+    common = ["bench.py", "--gpus", "1", "--frames", "9", "--steps", "2", "--warmup", "1"]
+    a = _run_bench(common + ["--dump-outputs", str(tmp_path / "a")])
+    b = _run_bench(common + ["--dump-outputs", str(tmp_path / "b")])
+    for line in (a, b):
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "roofline" not in line and "cpu_baseline" not in line
+        assert not {"flow_only_mpx_s", "lloyd_skip_fraction", "pruned_fit_check"} & set(line["config"])
+    names = ["centers.npy", "flow_sample.npy", "inertia.npy", "labels_sample.npy", "n_iter.npy"]
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    d = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert np.array_equal(d["centers"], np.array(a["config"]["centers"])) and float(d["inertia"]) == a["config"]["inertia"]
+    assert int(d["n_iter"]) == a["config"]["lloyd_iters"]
+    assert d["flow_sample"].shape == (8, 1 << 17, 2) and np.isfinite(d["flow_sample"]).all()
+    assert d["labels_sample"].shape == (8, 1 << 17) and set(np.unique(d["labels_sample"])) <= set(range(5))
 
 
 @pytest.mark.parametrize("W,H,T,batch", [(640, 360, 7, 4), (457, 263, 4, 3), (1920, 1080, 5, 2)])

@@ -196,3 +196,45 @@ def test_batch_schedule_and_auto_batch():
     for n in (1, 2, 37, 38, 75, 149, 150, 255, 256, 299, 999):
         sch = batch_schedule(n, bench.auto_batch(n))
         assert sum(sch) == n and max(sch) <= 64 and min(sch) >= 1
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs on the host side: the per-pixel results are sampled at the same seeded pixels of the same
+    seeded pairs on every call, converted to float32, and written one .npy per array within the size bound"""
+    import bench
+
+    class Buf:
+        def __init__(self, a):
+            self.a = a.view(np.uint8).ravel()
+
+        def download(self, shape, dtype, offset=0):
+            n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            assert offset + n <= self.a.nbytes
+            return self.a[offset:offset + n].view(dtype).reshape(shape).copy()
+
+    class Pipe:
+        W, H, n_pairs = 600, 300, 20
+
+    rng = np.random.default_rng(3)
+    flows = rng.standard_normal((Pipe.n_pairs, Pipe.H, Pipe.W, 2)).astype(np.float32)
+    labels = rng.integers(0, 5, (Pipe.n_pairs, Pipe.H, Pipe.W)).astype(np.uint8)
+    pipe = Pipe()
+    pipe.flows, pipe.labels = Buf(flows), Buf(labels)
+    a = bench.clip_outputs(pipe, 7, np.ones((5, 2)), 2.5, 11)
+    b = bench.clip_outputs(pipe, 7, np.ones((5, 2)), 2.5, 11)
+    assert a["flow_sample"].shape == (bench.DUMP_PAIRS, bench.DUMP_PIXELS, 2) and a["labels_sample"].dtype == np.float32
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    # the sample is the same (pair, pixel) positions of both results, drawn as bench.clip_outputs documents
+    sel = np.random.default_rng(0)
+    pairs = np.sort(sel.choice(Pipe.n_pairs, bench.DUMP_PAIRS, replace=False))
+    pix = np.sort(sel.choice(Pipe.W * Pipe.H, bench.DUMP_PIXELS, replace=False))
+    assert np.array_equal(a["flow_sample"], flows.reshape(Pipe.n_pairs, -1, 2)[pairs][:, pix])
+    assert np.array_equal(a["labels_sample"], labels.reshape(Pipe.n_pairs, -1)[pairs][:, pix])
+    assert np.array_equal(a["centers"], np.ones((5, 2))) and float(a["inertia"]) == 2.5
+    bench.dump_outputs(str(tmp_path / "d"), a)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in a)
+    assert float(np.load(tmp_path / "d" / "n_iter.npy")) == 11.0
+    assert sum(os.path.getsize(tmp_path / "d" / n) for n in os.listdir(tmp_path / "d")) <= bench.DUMP_MAX_BYTES
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"labels": labels})

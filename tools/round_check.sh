@@ -11,7 +11,7 @@ grep -h "unrelated content" gpurun_out/gputest.log
 timeout -k 10 300 python tools/parity_report.py > gpurun_out/parity.log 2>&1; tail -3 gpurun_out/parity.log
 bash tools/roofline_pmc.sh $tag > gpurun_out/roofline_pmc.log 2>&1 || { tail -20 gpurun_out/roofline_pmc.log; exit 1; }
 tail -5 gpurun_out/roofline_pmc.log | cut -c1-300
-timeout -k 10 600 python bench.py > profiles/${tag}_bench_line.json 2> gpurun_out/bench_default.err || { tail -20 gpurun_out/bench_default.err; exit 1; }
+err=$(mktemp); timeout -k 10 600 python bench.py --full > profiles/${tag}_bench_line.json 2> $err || { tail -20 $err; exit 1; }
 cut -c1-400 profiles/${tag}_bench_line.json
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for e in 2 1; do
