@@ -64,7 +64,7 @@ typedef struct ofc_fb_params {
     int levels;        /* 3   */
     int winsize;       /* 15  */
     int iterations;    /* 3   */
-    int poly_n;        /* 5   */
+    int poly_n;        /* 5   (5 or 7: the two sizes cv2 documents; others OFC_EUNSUPPORTED) */
     double poly_sigma; /* 1.2 */
     int flags;         /* 0   */
 } ofc_fb_params;
@@ -115,10 +115,11 @@ int ofc_flow_last_vis_dev(ofc_flow_t *f, const uint8_t **vis_dev);
 /* u8 frame -> f32 pyramid image of level k (GaussianBlur at full res + INTER_LINEAR resize) */
 int ofc_level_image(int device, const uint8_t *gray, int W, int H, const ofc_fb_params *p, int k,
                     float *out, int *w_out, int *h_out);
-/* FarnebackPolyExp: f32 HxW -> f32 HxWx5 {y-lin, x-lin, y^2, x^2, xy} */
+/* FarnebackPolyExp: f32 HxW -> f32 HxWx5 {y-lin, x-lin, y^2, x^2, xy}; n (poly_n) 5 or 7, else OFC_EUNSUPPORTED */
 int ofc_polyexp(int device, const float *img, int W, int H, int n, double sigma, float *R5);
 /* the same for pyramid level 0 straight from the u8 frame (level-0 blur fused in; what ofc_flow_* runs at level 0):
- * must equal ofc_level_image(k=0) followed by ofc_polyexp bit for bit.  OFC_EUNSUPPORTED when W < 4 or H < 2 */
+ * must equal ofc_level_image(k=0) followed by ofc_polyexp bit for bit.  n 5 or 7; OFC_EUNSUPPORTED otherwise and when
+ * W < 4 or H < 2 */
 int ofc_polyexp_u8(int device, const uint8_t *gray, int W, int H, int n, double sigma, float *R5);
 /* FarnebackUpdateMatrices: R0,R1 HxWx5, flow HxWx2 -> M HxWx5 */
 int ofc_update_matrices(int device, const float *R0, const float *R1, const float *flow, int W,

@@ -7,18 +7,19 @@ import csv
 
 import numpy as np
 
+from ._lib import FbParams
 from .computeOpticalFlowModule import ComputeOpticalFLow
 from .frameio import FrameSource, open_writer
 
 
-def run(input_path, device=0, quiet=False):
+def run(input_path, device=0, quiet=False, params=None):
     cap = FrameSource(input_path)                                           # :18
     number_of_videoFrames = cap.count                                       # :19
     output_onlyOpticalFlow = open_writer(input_path + "onlyOpticalflow.mp4", cap.fps, (cap.width, cap.height))  # :31-33
     ret, first_frame = cap.read()                                           # :39
     if not ret:
         raise RuntimeError(f"no frames in {input_path!r}")
-    flow = ComputeOpticalFLow(first_frame, device=device)                   # :58 prev_gray
+    flow = ComputeOpticalFLow(first_frame, device=device, params=params)    # :58 prev_gray
     x_values, y_values = [], []
     frameNum = 0
     while cap.isOpened():                                                   # :74
@@ -60,8 +61,10 @@ def main(argv=None):
     parser = argparse.ArgumentParser(prog="OpticalFlow", description="find optical flow of video")
     parser.add_argument("-i", "--input")
     parser.add_argument("--device", type=int, default=0)
+    parser.add_argument("--poly-n", type=int, default=5, help="polynomial expansion size (cv2 poly_n: 5 or 7)")
+    parser.add_argument("--poly-sigma", type=float, default=1.2, help="its Gaussian sigma (cv2 poly_sigma; 1.5 with 7)")
     args = parser.parse_args(argv)
-    run(args.input, device=args.device)
+    run(args.input, device=args.device, params=FbParams(poly_n=args.poly_n, poly_sigma=args.poly_sigma))
 
 
 if __name__ == "__main__":

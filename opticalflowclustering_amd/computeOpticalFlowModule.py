@@ -17,16 +17,17 @@ class ComputeOpticalFLow:
     """reference: computeOpticalFlowModule.py:6-36.  Holds one frame of state (prev_gray) on the device;
     compute(frame) returns a NEW HxWx3 uint8 BGR array each call (callers mutate it, KmeanGrids.py:108,277):
     BGR2GRAY -> calcOpticalFlowFarneback(prev, gray, None, 0.5, 3, 15, 3, 5, 1.2, 0) -> cartToPolar ->
-    H = angle*180/pi/2, S = 255, V = normalize(mag, 0, 255, MINMAX) (uint8 truncation) -> HSV2BGR."""
+    H = angle*180/pi/2, S = 255, V = normalize(mag, 0, 255, MINMAX) (uint8 truncation) -> HSV2BGR.
+    params: an FbParams for other calcOpticalFlowFarneback arguments (default: the reference's, above)."""
 
-    def __init__(self, firstframe, device=0):
+    def __init__(self, firstframe, device=0, params=None):
         self.firstframe = firstframe
         self.width = self.firstframe.shape[1]
         self.height = self.firstframe.shape[0]
         self.device = device
         self.last_mean_magnitude = None
         h = C.c_void_p()
-        p = FbParams()
+        p = params or FbParams()
         check(load().ofc_flow_create(device, self.width, self.height, C.byref(p), 1, C.byref(h)))
         self._h = h
         rc = load().ofc_flow_push_bgr(self._h, ptr(self._as_bgr(firstframe)), None, None, None)

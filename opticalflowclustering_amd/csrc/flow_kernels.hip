@@ -340,12 +340,12 @@ int launch_level_image(const uint8_t *src, float *dst, int nimg, int W0, int H0,
 //
 // Work-group = 256 threads = 4 waves, output strip 240 columns x rows_per_block rows, walked in chunks
 // of 8 rows:
-//   vertical pass   thread <-> column (250 = 240 + 2x5 halo columns, replicate-clamped).  Each thread keeps an
-//                   18-row register window of its column that slides down 8 rows per chunk; the 8 new rows
+//   vertical pass   thread <-> column (240 + 2N halo columns, replicate-clamped; N = poly_n = 5 or 7).  Each thread
+//                   keeps an (8 + 2N)-row register window of its column that slides down 8 rows per chunk; the 8 new rows
 //                   are requested right after the barrier (lanes <-> x: coalesced), so their latency hides
 //                   under the horizontal pass.  The window yields the three f32 moments t0,t1,t2 of 8 rows with
 //                   the symmetric / antisymmetric tap pairing of the reference -> LDS [3][8][256].
-//   horizontal pass wave <-> row, lane <-> 4 consecutive x: 12 ds_read_b128 (forced whole, see lds_read4),
+//   horizontal pass wave <-> row, lane <-> 4 consecutive x: 4 + 2N ds_read_b128 (forced whole, see lds_read4),
 //                   accumulators as described in the loop, 5 float4 stores per lane (1 KiB/wave-instruction).
 // 24 KB LDS, 146 VGPRs -> 3 waves/SIMD.  Measured ceilings on MI355X for this traffic shape (tools/membench):
 // 1 read : 5 write streams = 4.9 TB/s; this kernel's compute alone (stores off) = 5.9 TB/s-equivalent.
@@ -361,15 +361,15 @@ __device__ __forceinline__ float4 lds_read4(const float *p)
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
-constexpr int PE_N = 5;
 constexpr int PE_TX = 240;
-constexpr int PE_VW = PE_TX + 2 * PE_N;   // 250
 constexpr int PE_CH = 8;
 constexpr int PE_PLANE = 66;    // float4 per (row, pixel & 3) plane of the moments tile: 64 + 2 -> bank-staggered
 
+// N = poly_n, the half-width of the expansion window (cv2 documents 5 and 7; both are instantiated)
+template <int N>
 struct PolyArgs {
     int W, H, rows_per_block;
-    float g[PE_N + 1], xg[PE_N + 1], xxg[PE_N + 1];
+    float g[N + 1], xg[N + 1], xxg[N + 1];
     double ig11, ig03, ig33, ig55;
 };
 
@@ -380,10 +380,16 @@ struct PolyArgs {
 // representable in f32 whatever the evaluation order, so the result is bit-identical to k_level0 + this kernel.
 // F64H: the six horizontal sums exactly as the reference forms them (double accumulators; b1/b4 from double products, the
 // other four from float products) -- a study / fallback build (OFC_POLYEXP_F64=1): see DESIGN.md section 2.
-template <int TAG, bool U8IN, bool F64H = false>
+// N (last, so that the rocprof names of the poly_n=5 forms keep their prefix) is the window half-width: the strip needs
+// VW = 240 + 2N columns (250 / 254 <= 256 threads), the horizontal pass 4 + 2N moments per lane, whose highest LDS index
+// lane + (3 + 2N) / 4 = 63 at N = 7 stays inside the 66-float4 plane.
+template <int TAG, bool U8IN, bool F64H = false, int N = 5>
 __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv, float *__restrict__ R,
-                                                 PolyArgs p)
+                                                 PolyArgs<N> p)
 {
+    constexpr int VW = PE_TX + 2 * N;
+    static_assert(VW <= 256 && (VW - 1) / 4 < PE_PLANE && PE_TX / 4 - 1 + (3 + 2 * N) / 4 < PE_PLANE,
+                  "the strip and its halo must fit one work-group and one moments plane");
     // vertical moments of the chunk, one float4 (t0, t1, t2, t1) per pixel: the horizontal pass consumes them as the
     // register pairs (t0,t1) and (t2,t1), which is what lets it run on packed-f32 instructions.  Pixel p of the strip
     // lives at [p & 3][p >> 2]: lane l of the horizontal pass reads pixels 4l+j, so for a fixed j the 64 lanes touch 64
@@ -401,7 +407,7 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
     const float *img = U8IN ? nullptr : reinterpret_cast<const float *>(Iv) + (size_t)blockIdx.z * plane;
     const uint8_t *img8 = U8IN ? reinterpret_cast<const uint8_t *>(Iv) + (size_t)blockIdx.z * plane : nullptr;
     float *out = R + (size_t)blockIdx.z * 5 * plane;
-    const int xc = min(max(x0 - PE_N + tid, 0), W - 1);   // this thread's (clamped) column
+    const int xc = min(max(x0 - N + tid, 0), W - 1);   // this thread's (clamped) column
     const bool vec_ok = (W & 3) == 0;
 
     // U8IN: one (unaligned) dword per frame row holds the three horizontal taps of this column: bytes
@@ -418,43 +424,43 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
         return 0.25f * hval(hword(reflect101(r - 1, H))) + 0.5f * hval(hword(r)) + 0.25f * hval(hword(reflect101(r + 1, H)));
     };
     // strips whose rows (incl. the +-1 blur rows) need neither clamping nor reflection share the row-blurred samples
-    // between consecutive level-0 rows: 20 + 8 per chunk dword loads per thread, the count of the f32 path
-    const bool interior = U8IN && y_begin >= PE_N + 1 && y_begin + p.rows_per_block + 2 * PE_N + 2 <= H - 1;
+    // between consecutive level-0 rows: 10 + 2N + 8 per chunk dword loads per thread, the count of the f32 path
+    const bool interior = U8IN && y_begin >= N + 1 && y_begin + p.rows_per_block + 2 * N + 2 <= H - 1;
 
-    // register window of this thread's column: rows yc-5 .. yc+12; slides down 8 rows per chunk, the 8 new
+    // register window of this thread's column: rows yc-N .. yc+N+7; slides down 8 rows per chunk, the 8 new
     // rows are requested right after the barrier so that their HBM latency hides under the horizontal pass
-    float s[8 + 2 * PE_N], nxt[8];
+    float s[8 + 2 * N], nxt[8];
     uint32_t nxtw[8];
-    float hk0 = 0.f, hk1 = 0.f;                         // U8IN interior: row-blurred samples of window rows 18, 19
+    float hk0 = 0.f, hk1 = 0.f;                         // U8IN interior: row-blurred samples of window rows 8+2N, 9+2N
     if (!U8IN) {
 #pragma unroll
-        for (int j = 0; j < 8 + 2 * PE_N; j++)
-            s[j] = img[(size_t)min(max(y_begin - PE_N + j, 0), H - 1) * W + xc];
+        for (int j = 0; j < 8 + 2 * N; j++)
+            s[j] = img[(size_t)min(max(y_begin - N + j, 0), H - 1) * W + xc];
     } else if (interior) {
-        float hv[8 + 2 * PE_N + 2];
+        float hv[8 + 2 * N + 2];
 #pragma unroll
-        for (int j = 0; j < 8 + 2 * PE_N + 2; j++) hv[j] = hval(hword(y_begin - PE_N - 1 + j));
+        for (int j = 0; j < 8 + 2 * N + 2; j++) hv[j] = hval(hword(y_begin - N - 1 + j));
 #pragma unroll
-        for (int j = 0; j < 8 + 2 * PE_N; j++) s[j] = 0.25f * hv[j] + 0.5f * hv[j + 1] + 0.25f * hv[j + 2];
-        hk0 = hv[8 + 2 * PE_N];
-        hk1 = hv[8 + 2 * PE_N + 1];
+        for (int j = 0; j < 8 + 2 * N; j++) s[j] = 0.25f * hv[j] + 0.5f * hv[j + 1] + 0.25f * hv[j + 2];
+        hk0 = hv[8 + 2 * N];
+        hk1 = hv[8 + 2 * N + 1];
     } else {
 #pragma unroll
-        for (int j = 0; j < 8 + 2 * PE_N; j++) s[j] = i0_any(min(max(y_begin - PE_N + j, 0), H - 1));
+        for (int j = 0; j < 8 + 2 * N; j++) s[j] = i0_any(min(max(y_begin - N + j, 0), H - 1));
     }
 
     for (int yc = y_begin; yc < y_end; yc += PE_CH) {
         // ---- vertical pass ----
         // per tap pair: (a+b, b-a) in one packed add, (t0,t2) += (g,xxg)*(a+b) in one packed fma, t1 in a scalar fma:
         // 3 VALU instructions instead of 5, every lane-operation identical to the scalar form (same roundings)
-        if (tid < PE_VW) {
+        if (tid < VW) {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                v2f t02 = {s[i + PE_N] * p.g[0], 0.f};
+                v2f t02 = {s[i + N] * p.g[0], 0.f};
                 float t1 = 0.f;
 #pragma unroll
-                for (int k = 1; k <= PE_N; k++) {
-                    const float a = s[i + PE_N - k], b = s[i + PE_N + k];
+                for (int k = 1; k <= N; k++) {
+                    const float a = s[i + N - k], b = s[i + N + k];
                     const v2f pd = (v2f){b, b} + (v2f){a, -a};                     // (a + b, b - a)
                     t02 = __builtin_elementwise_fma((v2f){p.g[k], p.xxg[k]}, (v2f){pd.x, pd.x}, t02);
                     t1 = fmaf(p.xg[k], pd.y, t1);
@@ -467,13 +473,13 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
             if (!U8IN) {
 #pragma unroll
                 for (int j = 0; j < 8; j++)
-                    nxt[j] = img[(size_t)min(yc + PE_CH + PE_N + j, H - 1) * W + xc];
+                    nxt[j] = img[(size_t)min(yc + PE_CH + N + j, H - 1) * W + xc];
             } else if (interior) {
 #pragma unroll
-                for (int j = 0; j < 8; j++) nxtw[j] = hword(yc + PE_CH + PE_N + 1 + j);   // frame rows yc+14 .. yc+21
+                for (int j = 0; j < 8; j++) nxtw[j] = hword(yc + PE_CH + N + 1 + j);   // frame rows yc+N+9 .. yc+N+16
             } else {
 #pragma unroll
-                for (int j = 0; j < 8; j++) nxt[j] = i0_any(min(yc + PE_CH + PE_N + j, H - 1));
+                for (int j = 0; j < 8; j++) nxt[j] = i0_any(min(yc + PE_CH + N + j, H - 1));
             }
         }
         // ---- horizontal pass ----
@@ -482,9 +488,9 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
             if (y >= y_end) break;
             const int xo = x0 + 4 * lane;
             if (lane < PE_TX / 4 && xo < W) {
-                v2f A[14], Q[14];          // (t0, t1) and (t2, t1) of strip pixels 4*lane .. 4*lane + 13
+                v2f A[4 + 2 * N], Q[4 + 2 * N];   // (t0, t1) and (t2, t1) of strip pixels 4*lane .. 4*lane + 3 + 2N
 #pragma unroll
-                for (int j = 0; j < 14; j++) {
+                for (int j = 0; j < 4 + 2 * N; j++) {
                     const float4 v = lds_read4(reinterpret_cast<const float *>(&t4[rr][j & 3][lane + (j >> 2)]));
                     A[j] = (v2f){v.x, v.y};
                     Q[j] = (v2f){v.z, v.w};
@@ -492,8 +498,8 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
                 float r0[4], r1[4], r2[4], r3[4], r4[4];
 #pragma unroll
                 for (int o = 0; o < 4; o++) {
-                    const int c = o + PE_N;
-                    // The reference accumulates these six 11-tap sums in double.  Its inputs (the vertical moments) are
+                    const int c = o + N;
+                    // The reference accumulates these six (2N+1)-tap sums in double.  Its inputs (the vertical moments) are
                     // f32 already, each sum has only 6 terms, and the one place where rounding is amplified -- b1*ig03
                     // cancelling against b4|b5*ig33 in the second-derivative coefficients -- is evaluated in f64 below.
                     // f32 FMA accumulation costs <= ~3 ulp per sum; measured effect on the flow vs the oracle:
@@ -508,7 +514,7 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
                         double e1 = (double)(A[c].x * p.g[0]), e2 = 0, e3 = (double)(A[c].y * p.g[0]), e4 = 0,
                                e5 = (double)(Q[c].x * p.g[0]), e6 = 0;
 #pragma unroll
-                        for (int k = 1; k <= PE_N; k++) {
+                        for (int k = 1; k <= N; k++) {
                             const double tg = (double)(A[c + k].x + A[c - k].x);
                             e1 += tg * (double)p.g[k];
                             e4 += tg * (double)p.xxg[k];
@@ -528,7 +534,7 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
                     v2f b26 = {0.f, 0.f};                                // (b2, b6)
                     v2f b53 = Q[c] * (v2f){p.g[0], p.g[0]};              // (b5, b3)
 #pragma unroll
-                    for (int k = 1; k <= PE_N; k++) {
+                    for (int k = 1; k <= N; k++) {
                         const v2f sm = A[c + k] + A[c - k];              // (t0 sum, -)
                         const v2f df = A[c + k] - A[c - k];              // (t0 diff, t1 diff)
                         const v2f sq = Q[c + k] + Q[c - k];              // (t2 sum, t1 sum)
@@ -590,7 +596,7 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
         }
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 2 * PE_N; j++) s[j] = s[j + 8];
+        for (int j = 0; j < 2 * N; j++) s[j] = s[j + 8];
         if (U8IN && interior) {
             float hn[10];
             hn[0] = hk0;
@@ -598,18 +604,19 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
 #pragma unroll
             for (int j = 0; j < 8; j++) hn[2 + j] = hval(nxtw[j]);
 #pragma unroll
-            for (int j = 0; j < 8; j++) s[2 * PE_N + j] = 0.25f * hn[j] + 0.5f * hn[j + 1] + 0.25f * hn[j + 2];
+            for (int j = 0; j < 8; j++) s[2 * N + j] = 0.25f * hn[j] + 0.5f * hn[j + 1] + 0.25f * hn[j + 2];
             hk0 = hn[8];
             hk1 = hn[9];
         } else {
 #pragma unroll
-            for (int j = 0; j < 8; j++) s[2 * PE_N + j] = nxt[j];
+            for (int j = 0; j < 8; j++) s[2 * N + j] = nxt[j];
         }
     }
 }
 
 
-// OFC_POLYEXP_F64=1: horizontal sums in double, as the reference (read at every launch: a test toggles it)
+// OFC_POLYEXP_F64=1: horizontal sums in double, as the reference (read at every launch: a test toggles it).  Built for
+// poly_n = 5 only (it spills at 5 already): poly_n = 7 runs the f32 form whatever the switch says.
 static bool polyexp_f64()
 {
     const char *e = getenv("OFC_POLYEXP_F64");
@@ -628,13 +635,21 @@ int polyexp_default_rows(int W, int H, int nimg)
     return rows;
 }
 
-static void polyexp_args(PolyArgs &a, int W, int H, int nimg, const PolyConsts &c, int rows_per_block)
+template <int N>
+static void polyexp_args(PolyArgs<N> &a, int W, int H, int nimg, const PolyConsts &c, int rows_per_block)
 {
     a.W = W; a.H = H;
-    for (int i = 0; i <= PE_N; i++) { a.g[i] = c.g[i]; a.xg[i] = c.xg[i]; a.xxg[i] = c.xxg[i]; }
+    for (int i = 0; i <= N; i++) { a.g[i] = c.g[i]; a.xg[i] = c.xg[i]; a.xxg[i] = c.xxg[i]; }
     a.ig11 = c.ig11; a.ig03 = c.ig03; a.ig33 = c.ig33; a.ig55 = c.ig55;
     if (rows_per_block <= 0) rows_per_block = polyexp_default_rows(W, H, nimg);
     a.rows_per_block = cdiv(rows_per_block, PE_CH) * PE_CH;
+}
+
+int polyexp_n_check(int n)
+{
+    if (n == 5 || n == 7) return OFC_OK;
+    set_error("poly_n=%d unsupported: the polyexp kernel is built for poly_n 5 and 7", n);
+    return OFC_EUNSUPPORTED;
 }
 
 // polyexp of pyramid level 0 straight from the u8 frames (see U8IN); the caller checks polyexp_u8_ok()
@@ -646,13 +661,48 @@ bool polyexp_u8_ok(int W, int H, const LevelGeom &g)
     return k[0] == 0.25f && k[1] == 0.5f && k[2] == 0.25f;
 }
 
-int launch_polyexp_u8(const uint8_t *frames, float *R, int nimg, int W, int H, const PolyConsts &c, hipStream_t s)
+template <int N>
+static int launch_polyexp_u8_n(const uint8_t *frames, float *R, int nimg, int W, int H, const PolyConsts &c,
+                               hipStream_t s)
 {
-    PolyArgs a;
+    PolyArgs<N> a;
     polyexp_args(a, W, H, nimg, c, 0);
     dim3 grid(cdiv(W, PE_TX), cdiv(H, a.rows_per_block), nimg);
-    if (polyexp_f64()) hipLaunchKernelGGL((k_polyexp<0, true, true>), grid, dim3(256), 0, s, frames, R, a);
-    else hipLaunchKernelGGL((k_polyexp<0, true>), grid, dim3(256), 0, s, frames, R, a);
+    if constexpr (N == 5) {
+        if (polyexp_f64()) {
+            hipLaunchKernelGGL((k_polyexp<0, true, true, N>), grid, dim3(256), 0, s, frames, R, a);
+            OFC_HIP(hipGetLastError());
+            return OFC_OK;
+        }
+    }
+    hipLaunchKernelGGL((k_polyexp<0, true, false, N>), grid, dim3(256), 0, s, frames, R, a);
+    OFC_HIP(hipGetLastError());
+    return OFC_OK;
+}
+
+int launch_polyexp_u8(const uint8_t *frames, float *R, int nimg, int W, int H, const PolyConsts &c, hipStream_t s)
+{
+    if (c.n == 5) return launch_polyexp_u8_n<5>(frames, R, nimg, W, H, c, s);
+    if (c.n == 7) return launch_polyexp_u8_n<7>(frames, R, nimg, W, H, c, s);
+    return polyexp_n_check(c.n);
+}
+
+template <int N>
+static int launch_polyexp_n(const float *I, float *R, int nimg, int W, int H, const PolyConsts &c,
+                            int rows_per_block, hipStream_t s, bool bench_tag)
+{
+    PolyArgs<N> a;
+    polyexp_args(a, W, H, nimg, c, rows_per_block);
+    dim3 grid(cdiv(W, PE_TX), cdiv(H, a.rows_per_block), nimg);
+    if constexpr (N == 5) {
+        if (polyexp_f64()) {
+            hipLaunchKernelGGL((k_polyexp<2, false, true, N>), grid, dim3(256), 0, s, I, R, a);
+            OFC_HIP(hipGetLastError());
+            return OFC_OK;
+        }
+    }
+    if (bench_tag) hipLaunchKernelGGL((k_polyexp<1, false, false, N>), grid, dim3(256), 0, s, I, R, a);
+    else hipLaunchKernelGGL((k_polyexp<0, false, false, N>), grid, dim3(256), 0, s, I, R, a);
     OFC_HIP(hipGetLastError());
     return OFC_OK;
 }
@@ -660,14 +710,9 @@ int launch_polyexp_u8(const uint8_t *frames, float *R, int nimg, int W, int H, c
 int launch_polyexp(const float *I, float *R, int nimg, int W, int H, const PolyConsts &c,
                    int rows_per_block, hipStream_t s, bool bench_tag)
 {
-    PolyArgs a;
-    polyexp_args(a, W, H, nimg, c, rows_per_block);
-    dim3 grid(cdiv(W, PE_TX), cdiv(H, a.rows_per_block), nimg);
-    if (polyexp_f64()) hipLaunchKernelGGL((k_polyexp<2, false, true>), grid, dim3(256), 0, s, I, R, a);
-    else if (bench_tag) hipLaunchKernelGGL((k_polyexp<1, false>), grid, dim3(256), 0, s, I, R, a);
-    else hipLaunchKernelGGL((k_polyexp<0, false>), grid, dim3(256), 0, s, I, R, a);
-    OFC_HIP(hipGetLastError());
-    return OFC_OK;
+    if (c.n == 5) return launch_polyexp_n<5>(I, R, nimg, W, H, c, rows_per_block, s, bench_tag);
+    if (c.n == 7) return launch_polyexp_n<7>(I, R, nimg, W, H, c, rows_per_block, s, bench_tag);
+    return polyexp_n_check(c.n);
 }
 
 // (the per-pixel update-matrices arithmetic -- um_load / um_math -- lives in flow_device.h)

@@ -101,6 +101,7 @@ void polyexp_setup(int n, double sigma, PolyConsts &c)
     s = 1. / s;
     for (int x = -n; x <= n; x++) gf[x + n] = (float)(gf[x + n] * s);
     memset(&c, 0, sizeof(c));
+    c.n = n;
     for (int x = 0; x <= n && x < 8; x++) {
         c.g[x] = gf[x + n];
         c.xg[x] = (float)(x * c.g[x]);
@@ -133,11 +134,7 @@ static int check_params(const ofc_fb_params &p, int W, int H)
         set_error("flags=%d: only the box-filter variant (flags 0) the reference uses is implemented", p.flags);
         return OFC_EUNSUPPORTED;
     }
-    if (p.poly_n != 5) {
-        set_error("poly_n=%d: the polyexp kernel is specialised for poly_n=5 (the reference's value)", p.poly_n);
-        return OFC_EUNSUPPORTED;
-    }
-    return OFC_OK;
+    return polyexp_n_check(p.poly_n);
 }
 
 }  // namespace ofc
@@ -616,7 +613,7 @@ int ofc_polyexp(int device, const float *img, int W, int H, int n, double sigma,
 {
     OFC_REQUIRE(img && R5, "null pointer");
     OFC_REQUIRE(W >= 1 && H >= 1, "bad size");
-    if (n != 5) { set_error("poly_n=%d unsupported (kernel specialised for 5)", n); return OFC_EUNSUPPORTED; }
+    OFC_TRY(polyexp_n_check(n));
     OFC_TRY(ensure_device(device));
     const size_t P = (size_t)W * H;
     PolyConsts pc;
@@ -633,9 +630,9 @@ int ofc_polyexp(int device, const float *img, int W, int H, int n, double sigma,
 int ofc_polyexp_u8(int device, const uint8_t *gray, int W, int H, int n, double sigma, float *R5)
 {
     OFC_REQUIRE(gray && R5 && W >= 1 && H >= 1, "bad arguments");
-    if (n != 5) { set_error("poly_n %d unsupported (5 only)", n); return OFC_EUNSUPPORTED; }
+    OFC_TRY(polyexp_n_check(n));
     OFC_TRY(ensure_device(device));
-    ofc_fb_params prm = {0.5, 0, 15, 3, 5, sigma, 0};
+    ofc_fb_params prm = {0.5, 0, 15, 3, n, sigma, 0};
     const LevelGeom g = level_geometry(W, H, prm, 0);
     if (!polyexp_u8_ok(W, H, g)) { set_error("fused level-0 expansion needs W >= 4 and H >= 2"); return OFC_EUNSUPPORTED; }
     const size_t P = (size_t)W * H;

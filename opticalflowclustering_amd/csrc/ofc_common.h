@@ -77,10 +77,12 @@ int pyramid_levels(int W, int H, const ofc_fb_params &p);
 LevelGeom level_geometry(int W, int H, const ofc_fb_params &p, int k);
 void gaussian_kernel(int n, double sigma, float *k);           // getGaussianKernel, CV_32F
 struct PolyConsts {
+    int n;                                  // poly_n: the launchers dispatch on it (5 and 7 are built)
     float g[8], xg[8], xxg[8];
     double ig11, ig03, ig33, ig55;
 };
 void polyexp_setup(int n, double sigma, PolyConsts &c);        // FarnebackPrepareGaussian
+int polyexp_n_check(int n);        // OFC_OK for the built poly_n (5, 7), else OFC_EUNSUPPORTED with the message set
 
 // ---- kernel launchers (flow_kernels.hip) : device pointers, asynchronous on `s` ----
 // src: [nimg][H0][W0] u8 -> dst: [nimg][h][w] f32

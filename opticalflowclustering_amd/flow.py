@@ -1,6 +1,9 @@
 """Farneback flow engine (libofc ofc_flow_*): the device-side replacement of
-cv2.calcOpticalFlowFarneback as called at computeOpticalFlowModule.py:20-22."""
+cv2.calcOpticalFlowFarneback as called at computeOpticalFlowModule.py:20-22, and calcOpticalFlowFarneback itself
+with cv2's call shape."""
 import ctypes as C
+import threading
+from collections import OrderedDict
 
 import numpy as np
 
@@ -18,15 +21,19 @@ class FlowEngine:
         check(load().ofc_flow_create(device, self.W, self.H, C.byref(self.params), self.max_batch, C.byref(h)))
         self._h = h
 
-    def calc(self, prev_gray, next_gray):
-        """one isolated pair, host arrays -> HxWx2 float32 (u = x-displacement, v = y-displacement)"""
+    def calc(self, prev_gray, next_gray, out=None):
+        """one isolated pair, host arrays -> HxWx2 float32 (u = x-displacement, v = y-displacement); `out`: a
+        C-contiguous HxWx2 float32 array to write the flow into (returned)"""
         prev_gray = np.ascontiguousarray(prev_gray, np.uint8)
         next_gray = np.ascontiguousarray(next_gray, np.uint8)
         if prev_gray.shape != (self.H, self.W) or next_gray.shape != (self.H, self.W):
             raise ValueError(f"expected two {self.H}x{self.W} uint8 images")
-        flow = np.empty((self.H, self.W, 2), np.float32)
-        check(load().ofc_flow_calc(self._h, ptr(prev_gray), ptr(next_gray), ptr(flow)))
-        return flow
+        if out is None:
+            out = np.empty((self.H, self.W, 2), np.float32)
+        elif not _is_flow_buffer(out, self.H, self.W):
+            raise ValueError(f"out must be a writeable C-contiguous {self.H}x{self.W}x2 float32 array")
+        check(load().ofc_flow_calc(self._h, ptr(prev_gray), ptr(next_gray), ptr(out)))
+        return out
 
     def push(self, gray):
         """streaming: returns None for the first frame, then the flow prev->gray"""
@@ -64,3 +71,58 @@ class FlowEngine:
             self.close()
         except Exception:
             pass
+
+
+def _is_flow_buffer(a, H, W):
+    return (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.shape == (H, W, 2)
+            and a.flags.c_contiguous and a.flags.writeable)
+
+
+# ---- cv2.calcOpticalFlowFarneback ----
+OPTFLOW_USE_INITIAL_FLOW = 4        # cv2's flag values; neither is implemented: the library refuses both
+OPTFLOW_FARNEBACK_GAUSSIAN = 256
+
+_FB_CACHE_MAX = 4                   # engines kept alive (each owns its device scratch); least recently used goes first
+_fb_engines = OrderedDict()         # (device, W, H, parameters) -> FlowEngine
+_fb_lock = threading.Lock()         # engine handles are not thread-safe (ofc.h)
+
+
+def _gray_arg(a, name):
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 2:
+        raise ValueError(f"{name} must be a 2-D uint8 array (one grey frame)")
+    return np.ascontiguousarray(a)
+
+
+def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags,
+                             device=0):
+    """cv2.calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
+    on the GPU.  prev / next: HxW uint8 frames.  Returns the HxWx2 float32 flow: written into `flow` (and that object
+    returned) when it is a writeable C-contiguous HxWx2 float32 array, a new array otherwise.  poly_n 5 or 7; flags
+    must be 0 (OPTFLOW_USE_INITIAL_FLOW / OPTFLOW_FARNEBACK_GAUSSIAN raise OfcError OFC_EUNSUPPORTED).  One engine
+    per (device, size, parameters) is kept between calls."""
+    prev = _gray_arg(prev, "prev")
+    next = _gray_arg(next, "next")
+    if prev.shape != next.shape:
+        raise ValueError(f"prev {prev.shape} and next {next.shape} differ in shape")
+    H, W = prev.shape
+    out = flow if _is_flow_buffer(flow, H, W) else np.empty((H, W, 2), np.float32)
+    key = (int(device), W, H, float(pyr_scale), int(levels), int(winsize), int(iterations), int(poly_n),
+           float(poly_sigma), int(flags))
+    with _fb_lock:
+        eng = _fb_engines.get(key)
+        if eng is None:
+            eng = FlowEngine(W, H, FbParams(*key[3:]), max_batch=1, device=key[0])
+            _fb_engines[key] = eng
+            while len(_fb_engines) > _FB_CACHE_MAX:
+                _fb_engines.popitem(last=False)[1].close()
+        else:
+            _fb_engines.move_to_end(key)
+        eng.calc(prev, next, out)
+    return out
+
+
+def clear_farneback_cache():
+    """close the engines calcOpticalFlowFarneback keeps (frees their device memory)"""
+    with _fb_lock:
+        while _fb_engines:
+            _fb_engines.popitem()[1].close()
