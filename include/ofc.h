@@ -62,12 +62,13 @@ int ofc_device_sync(int device);
 typedef struct ofc_fb_params {
     double pyr_scale;  /* 0.5 */
     int levels;        /* 3   */
-    int winsize;       /* 15  */
+    int winsize;       /* 15  (odd, 5 .. OFC_WINSIZE_MAX; even OFC_EINVAL, wider OFC_EUNSUPPORTED) */
     int iterations;    /* 3   */
     int poly_n;        /* 5   (5 or 7: the two sizes cv2 documents; others OFC_EUNSUPPORTED) */
     double poly_sigma; /* 1.2 */
     int flags;         /* 0   */
 } ofc_fb_params;
+#define OFC_WINSIZE_MAX 255 /* widest Farneback window the engine implements */
 
 void ofc_fb_default_params(ofc_fb_params *p);
 
@@ -124,7 +125,8 @@ int ofc_polyexp_u8(int device, const uint8_t *gray, int W, int H, int n, double 
 /* FarnebackUpdateMatrices: R0,R1 HxWx5, flow HxWx2 -> M HxWx5 */
 int ofc_update_matrices(int device, const float *R0, const float *R1, const float *flow, int W,
                         int H, float *M);
-/* box mean (winsize) of M + 2x2 solve: M HxWx5 -> flow HxWx2 */
+/* box mean (winsize) of M + 2x2 solve: M HxWx5 -> flow HxWx2.  winsize odd, 5 .. OFC_WINSIZE_MAX (19 and wider use the
+ * window-independent kernel the engine runs for them); others OFC_EUNSUPPORTED */
 int ofc_box_solve(int device, const float *M, int W, int H, int winsize, float *flow);
 /* resize(flow, (w,h), INTER_LINEAR) * mul */
 int ofc_flow_resize(int device, const float *flow, int sw, int sh, int dw, int dh, float mul,

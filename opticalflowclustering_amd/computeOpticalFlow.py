@@ -61,10 +61,12 @@ def main(argv=None):
     parser = argparse.ArgumentParser(prog="OpticalFlow", description="find optical flow of video")
     parser.add_argument("-i", "--input")
     parser.add_argument("--device", type=int, default=0)
+    parser.add_argument("--winsize", type=int, default=15, help="averaging window (cv2 winsize: odd, 5 .. 255)")
     parser.add_argument("--poly-n", type=int, default=5, help="polynomial expansion size (cv2 poly_n: 5 or 7)")
     parser.add_argument("--poly-sigma", type=float, default=1.2, help="its Gaussian sigma (cv2 poly_sigma; 1.5 with 7)")
     args = parser.parse_args(argv)
-    run(args.input, device=args.device, params=FbParams(poly_n=args.poly_n, poly_sigma=args.poly_sigma))
+    run(args.input, device=args.device, params=FbParams(winsize=args.winsize, poly_n=args.poly_n,
+                                                                  poly_sigma=args.poly_sigma))
 
 
 if __name__ == "__main__":

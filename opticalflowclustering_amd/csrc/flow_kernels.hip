@@ -846,9 +846,170 @@ int box_default_rows(int W, int H, int npair)
     return rows;
 }
 
+// ------------------------------------------------------------------------------------------------
+// K5 for wide windows (winsize 19 .. OFC_WINSIZE_MAX): the same box mean + solve with a cost per pixel that does not
+// depend on m = winsize / 2.
+//
+// A work-group owns a SPAN of 1024 columns (4 consecutive per lane) starting m + 1 columns left of its TX = 1024 - 2m - 1
+// output columns, and marches down a strip of rows.  Each lane keeps the f64 vertical sums of its 4 columns in registers
+// (+ new row - old row, 2 loads per channel per row, as in k_box_solve).  Every row the work-group forms the inclusive
+// prefix P of those sums over the span (in-lane serial, wave scan, wave totals through LDS) with columns outside the
+// frame counted as 0, so that the in-frame part of the window is S(x) = P(x+m) - P(x-m-1) -- two LDS reads per channel
+// whatever m is -- and the replicated border adds (x+m-(W-1))+ * v[W-1] + (m-x)+ * v[0].  Every output that needs such a
+// term has that edge column inside its span.  Windows wider than the frame (coarse levels) follow from the same formula.
+// f64 throughout; the prefix difference is exact up to ~1e-16 of the row's running total.
+// ------------------------------------------------------------------------------------------------
+constexpr int BW_SPAN = 1024;      // columns of vertical sums a work-group scans per row (4 per lane)
+
+__global__ __launch_bounds__(256, 3) void k_box_solve_wide(const float *__restrict__ Mb, float *__restrict__ flowb,
+                                                        int W, int H, int m, int rows_per_block)
+{
+    __shared__ __align__(16) double P[5][BW_SPAN];      // 40 KB: this row's prefix over the span
+    __shared__ double wtot[5][4];                       // per-wave totals of the scan
+    __shared__ double edge[2][5];                       // vertical sums of columns 0 and W-1 (when inside the span)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int TX = BW_SPAN - 2 * m - 1;
+    const int x0 = blockIdx.x * TX, a0 = x0 - m - 1;   // first output column, first span column
+    const int y_begin = blockIdx.y * rows_per_block;
+    const int y_end = min(y_begin + rows_per_block, H);
+    const size_t plane = (size_t)W * H;
+    const float *Mp = Mb + (size_t)blockIdx.z * 5 * plane;
+    float2 *flow = reinterpret_cast<float2 *>(flowb) + (size_t)blockIdx.z * plane;
+    const double scale = 1.0 / ((2 * m + 1) * (2 * m + 1));
+
+    // this lane's span columns a0 + 4*tid + i; out-of-frame ones load the clamped column (a valid address) and count 0
+    int col[4];
+    bool in[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int c = a0 + 4 * tid + i;
+        in[i] = c >= 0 && c < W;
+        col[i] = min(max(c, 0), W - 1);
+    }
+
+    // vertical sums of rows [y_begin-m, y_begin+m] (replicate): the rows inside the frame once each, the repeated edge
+    // rows as a multiple -- at most min(2m+1, H) row loads, so a window taller than a coarse level costs no more
+    double v[5][4];
+#pragma unroll
+    for (int c = 0; c < 5; c++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) v[c][i] = 0;
+    const int jlo = max(y_begin - m, 0), jhi = min(y_begin + m, H - 1);
+    for (int j = jlo; j <= jhi; j++) {
+        const size_t ro = (size_t)j * W;
+#pragma unroll
+        for (int c = 0; c < 5; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[c][i] += (double)Mp[c * plane + ro + col[i]];
+    }
+    const double ntop = (double)max(m - y_begin, 0), nbot = (double)max(y_begin + m - (H - 1), 0);
+    if (ntop > 0 || nbot > 0) {
+#pragma unroll
+        for (int c = 0; c < 5; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                v[c][i] += ntop * (double)Mp[c * plane + col[i]] + nbot * (double)Mp[c * plane + (size_t)(H - 1) * W + col[i]];
+    }
+
+    for (int y = y_begin; y < y_end; y++) {
+        // the incoming row that advances the sums to y+1, issued before this row's scan (the outgoing one, issued after
+        // it, leaves the register budget of 3 waves per SIMD)
+        float fa[5][4];
+        const size_t oa = (size_t)min(y + 1 + m, H - 1) * W, os = (size_t)max(y - m, 0) * W;
+#pragma unroll
+        for (int c = 0; c < 5; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) fa[c][i] = Mp[c * plane + oa + col[i]];
+
+        // only the lane's exclusive offset crosses the barrier; its 4 in-lane prefixes are formed again from v after it
+        double ex[5];
+#pragma unroll
+        for (int c = 0; c < 5; c++) {
+            double s = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) s += in[i] ? v[c][i] : 0.0;
+            double t = s;                               // inclusive wave scan of the lane totals
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const double o = __shfl_up(t, d);
+                if (lane >= d) t += o;
+            }
+            ex[c] = __shfl_up(t, 1);
+            if (lane == 0) ex[c] = 0;
+            if (lane == 63) wtot[c][wave] = t;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 5; c++) {
+            double off = ex[c];
+            for (int w = 0; w < wave; w++) off += wtot[c][w];
+            double p[4], s = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                s += in[i] ? v[c][i] : 0.0;
+                p[i] = s + off;
+            }
+            *reinterpret_cast<double2 *>(&P[c][4 * tid]) = make_double2(p[0], p[1]);
+            *reinterpret_cast<double2 *>(&P[c][4 * tid + 2]) = make_double2(p[2], p[3]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (in[i] && col[i] == 0)
+#pragma unroll
+                for (int c = 0; c < 5; c++) edge[0][c] = v[c][i];
+            if (in[i] && col[i] == W - 1)
+#pragma unroll
+                for (int c = 0; c < 5; c++) edge[1][c] = v[c][i];
+        }
+        __syncthreads();
+        for (int j = tid; j < TX; j += 256) {
+            const int x = x0 + j;
+            if (x >= W) break;
+            const double nr = (double)max(x + m - (W - 1), 0), nl = (double)max(m - x, 0);
+            double S[5];
+#pragma unroll
+            for (int c = 0; c < 5; c++) {
+                S[c] = P[c][j + 2 * m + 1] - P[c][j];
+                if (nr > 0) S[c] += nr * edge[1][c];
+                if (nl > 0) S[c] += nl * edge[0][c];
+            }
+            const double g11 = S[0] * scale, g12 = S[1] * scale, g22 = S[2] * scale, h1 = S[3] * scale,
+                         h2 = S[4] * scale;
+            const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
+            flow[(size_t)y * W + x] = make_float2((float)((g11 * h2 - g12 * h1) * idet),
+                                                  (float)((g22 * h1 - g12 * h2) * idet));
+        }
+        __syncthreads();   // P and edge are rewritten by the next row
+#pragma unroll
+        for (int c = 0; c < 5; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[c][i] += (double)fa[c][i] - (double)Mp[c * plane + os + col[i]];
+    }
+}
+
+// strips two windows tall (the prologue sums 2m+1 rows per column: <= 1/4 of a strip's loads), at least 64 rows.  A
+// function of the window alone, so that a pair's flow does not depend on the batch it was computed in.
+int box_wide_rows(int winsize) { return std::max(2 * winsize, 64); }
+
+static int launch_box_solve_wide(const float *M, float *flow, int npair, int W, int H, int winsize,
+                                 int rows_per_block, hipStream_t s)
+{
+    if (!(winsize & 1) || winsize < WINSIZE_WIDE_MIN || winsize > OFC_WINSIZE_MAX) {
+        set_error("winsize %d unsupported (odd 5..%d)", winsize, OFC_WINSIZE_MAX);
+        return OFC_EUNSUPPORTED;
+    }
+    if (rows_per_block <= 0) rows_per_block = box_wide_rows(winsize);
+    const int m = winsize / 2;
+    dim3 grid(cdiv(W, BW_SPAN - 2 * m - 1), cdiv(H, rows_per_block), npair);
+    hipLaunchKernelGGL(k_box_solve_wide, grid, dim3(256), 0, s, M, flow, W, H, m, rows_per_block);
+    OFC_HIP(hipGetLastError());
+    return OFC_OK;
+}
+
 int launch_box_solve(const float *M, float *flow, int npair, int W, int H, int winsize,
                      int rows_per_block, hipStream_t s)
 {
+    if (winsize >= WINSIZE_WIDE_MIN) return launch_box_solve_wide(M, flow, npair, W, H, winsize, rows_per_block, s);
     if (rows_per_block <= 0) rows_per_block = box_default_rows(W, H, npair);
     rows_per_block = cdiv(rows_per_block, BS_ROWS) * BS_ROWS;
     dim3 block(256);
@@ -867,7 +1028,7 @@ int launch_box_solve(const float *M, float *flow, int npair, int W, int H, int w
         OFC_BOX_CASE(7)
         OFC_BOX_CASE(8)
     default:
-        set_error("winsize %d unsupported (odd 5..17)", winsize);
+        set_error("winsize %d unsupported (odd 5..%d)", winsize, OFC_WINSIZE_MAX);
         return OFC_EUNSUPPORTED;
     }
 #undef OFC_BOX_CASE

@@ -134,6 +134,10 @@ static int check_params(const ofc_fb_params &p, int W, int H)
         set_error("flags=%d: only the box-filter variant (flags 0) the reference uses is implemented", p.flags);
         return OFC_EUNSUPPORTED;
     }
+    if ((p.winsize & 1) && p.winsize > OFC_WINSIZE_MAX) {      // (even windows: OFC_EINVAL where a window is used)
+        set_error("winsize %d unsupported (odd 5..%d)", p.winsize, OFC_WINSIZE_MAX);
+        return OFC_EUNSUPPORTED;
+    }
     return polyexp_n_check(p.poly_n);
 }
 
@@ -220,7 +224,8 @@ struct ofc_flow {
     std::vector<LevelGeom> geom;    // [0..levels]
     hipStream_t stream = nullptr;
     DevBuf I, R, M, flowA, flowB, flowC;   // scratch sized for level 0 and max_batch
-    bool fused = true;              // update-matrices fused into the box/solve kernel (winsize <= 15)
+    bool fused = true;              // update-matrices fused into the box/solve kernel (winsize <= 15); otherwise the staged
+                                    // kernels: k_box_solve<8> at 17, k_box_solve_wide from 19 on
     bool fuse_level0 = true;        // polyexp of level 0 reads the u8 frames (no f32 level-0 image)
     bool fuse2 = false;             // iterations 2+3 of a level in one launch (k_flow_iter2): measured SLOWER than two launches
                                     // on MI355X, kept as an opt-in experiment: OFC_FLOW_FUSE2=1 ...

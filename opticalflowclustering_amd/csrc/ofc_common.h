@@ -83,6 +83,7 @@ struct PolyConsts {
 };
 void polyexp_setup(int n, double sigma, PolyConsts &c);        // FarnebackPrepareGaussian
 int polyexp_n_check(int n);        // OFC_OK for the built poly_n (5, 7), else OFC_EUNSUPPORTED with the message set
+constexpr int WINSIZE_WIDE_MIN = 19;   // launch_box_solve: this winsize and wider run k_box_solve_wide (up to OFC_WINSIZE_MAX)
 
 // ---- kernel launchers (flow_kernels.hip) : device pointers, asynchronous on `s` ----
 // src: [nimg][H0][W0] u8 -> dst: [nimg][h][w] f32
@@ -124,5 +125,6 @@ int launch_flow_iter_stamped(const float *R, size_t frame_stride_R, const float 
                              int H, hipStream_t s, unsigned long long *dbg, int *grid_out);
 int polyexp_default_rows(int W, int H, int nimg);
 int box_default_rows(int W, int H, int npair);
+int box_wide_rows(int winsize);   // strip height of k_box_solve_wide
 
 }  // namespace ofc

@@ -97,9 +97,10 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
                              device=0):
     """cv2.calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
     on the GPU.  prev / next: HxW uint8 frames.  Returns the HxWx2 float32 flow: written into `flow` (and that object
-    returned) when it is a writeable C-contiguous HxWx2 float32 array, a new array otherwise.  poly_n 5 or 7; flags
-    must be 0 (OPTFLOW_USE_INITIAL_FLOW / OPTFLOW_FARNEBACK_GAUSSIAN raise OfcError OFC_EUNSUPPORTED).  One engine
-    per (device, size, parameters) is kept between calls."""
+    returned) when it is a writeable C-contiguous HxWx2 float32 array, a new array otherwise.  winsize odd, 5 .. 255
+    (wider raises OfcError OFC_EUNSUPPORTED, even OFC_EINVAL); poly_n 5 or 7; flags must be 0
+    (OPTFLOW_USE_INITIAL_FLOW / OPTFLOW_FARNEBACK_GAUSSIAN raise OfcError OFC_EUNSUPPORTED).  One engine per (device,
+    size, parameters) is kept between calls; parameters the library refuses leave none behind."""
     prev = _gray_arg(prev, "prev")
     next = _gray_arg(next, "next")
     if prev.shape != next.shape:
