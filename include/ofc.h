@@ -301,7 +301,9 @@ int ofc_grid_cell_mean_flow(int device, const float *flow, int W, int H, int row
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.
- * sims has n_large-n_small+1 entries; 0 where either norm is 0.  Integer-valued input is summed exactly.
+ * sims has n_large-n_small+1 entries; 0 where either norm is 0.  Integer-valued input (the hue columns) is summed exactly
+ * in 64-bit integers as long as n_small * max(|small|, |large|)^2 < 2^63; larger integers and non-integer input are
+ * summed in f64, each of the three sums to n_small * 2^-53 relative.
  * ------------------------------------------------------------------------------------------ */
 int ofc_sliding_cosine(int device, const double *small_v, int n_small, const double *large_v, int n_large,
                        double *sims);

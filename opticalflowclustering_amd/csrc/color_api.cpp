@@ -197,9 +197,23 @@ int ofc_sliding_cosine(int device, const double *small_v, int n_small, const dou
     OFC_REQUIRE(n_small >= 1 && n_large >= n_small, "need 1 <= n_small <= n_large (got %d, %d)", n_small, n_large);
     OFC_TRY(ensure_device(device));
     const int nwin = n_large - n_small + 1;
+    // The integer path needs every value integral and every partial sum of x*x, y*y, x*y inside int64: with
+    // ms = max|small|, ml = max|large| that holds when n_small * max(ms, ml)^2 < 2^63 (exact in 128 bits: 31 + 62 bits).
+    // Anything else, large integers included, goes through the f64 sums.
     int all_int = 1;
-    for (int i = 0; i < n_small && all_int; i++) all_int = std::fabs(small_v[i]) < 2147483648.0 && small_v[i] == std::floor(small_v[i]);
-    for (int i = 0; i < n_large && all_int; i++) all_int = std::fabs(large_v[i]) < 2147483648.0 && large_v[i] == std::floor(large_v[i]);
+    double ms = 0, ml = 0;
+    for (int i = 0; i < n_small && all_int; i++) {
+        all_int = std::fabs(small_v[i]) < 2147483648.0 && small_v[i] == std::floor(small_v[i]);
+        ms = std::max(ms, std::fabs(small_v[i]));
+    }
+    for (int i = 0; i < n_large && all_int; i++) {
+        all_int = std::fabs(large_v[i]) < 2147483648.0 && large_v[i] == std::floor(large_v[i]);
+        ml = std::max(ml, std::fabs(large_v[i]));
+    }
+    if (all_int) {
+        const unsigned __int128 m = (unsigned __int128)(uint64_t)std::max(ms, ml);
+        all_int = (unsigned __int128)(uint64_t)n_small * m * m < ((unsigned __int128)1 << 63);
+    }
     DevBuf a, b, o;
     OFC_TRY(a.alloc(sizeof(double) * n_small));
     OFC_TRY(b.alloc(sizeof(double) * n_large));

@@ -339,8 +339,8 @@ int launch_grid_cell_mean_flow(const float *flow, int W, int H, int npair, int r
 
 // ------------------------------------------------------------------------------------------------
 // sliding-window cosine similarity (findCosineDifferentVectors.py:5-61): one work-group per window offset.
-// np.dot / np.linalg.norm on the integer hue columns are exact integer sums; a value v with |v| < 2^31 and integral
-// goes through the int64 accumulators, anything else through f64 (tree order).
+// np.dot / np.linalg.norm on the integer hue columns are exact integer sums; integral input whose sums cannot leave
+// int64 (the host checks n * max|v|^2 < 2^63) goes through the int64 accumulators, anything else through f64 (tree order).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sliding_cosine(const double *__restrict__ a, int na,
                                                         const double *__restrict__ b, double *__restrict__ sims,

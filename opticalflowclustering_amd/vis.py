@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, load, ptr
+from ._lib import DeviceBuffer, check, load, ptr
 
 
 def bgr2gray(bgr, device=0):
@@ -22,6 +22,38 @@ def flow_to_bgr(flow, device=0):
     mm = C.c_float()
     check(load().ofc_flow_to_bgr(device, ptr(flow), W, H, ptr(out), C.byref(mm)))
     return out, mm.value
+
+
+def flow_to_bgr_frames(flows, want_mean=True, device=0):
+    """flow_to_bgr on n device-resident frames in one call (each frame normalised by its own min/max):
+    (n, H, W, 2) f32 -> ((n, H, W, 3) u8, np.mean(magnitude) per frame (n,) f32, or None if not asked for)"""
+    flows = np.ascontiguousarray(flows, np.float32)
+    n, H, W = flows.shape[:3]
+    src, dst = DeviceBuffer(flows.nbytes, device).upload(flows), DeviceBuffer(n * H * W * 3, device)
+    mean = DeviceBuffer(4 * n, device) if want_mean else None
+    try:
+        check(load().ofc_flow_to_bgr_dev(device, src.ptr, W, H, n, dst.ptr, mean.ptr if mean else None))
+        return dst.download((n, H, W, 3), np.uint8), mean.download(n, np.float32) if mean else None
+    finally:
+        for b in (src, dst, mean):
+            if b:
+                b.free()
+
+
+def bgr2hsv(bgr, device=0):
+    """cv2.cvtColor(BGR2HSV) on (..., 3) u8, H in [0, 180)"""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    out = np.empty_like(bgr)
+    check(load().ofc_bgr2hsv(device, ptr(bgr), bgr.size // 3, ptr(out)))
+    return out
+
+
+def preprocess_rgba(img3, thresh=30, device=0):
+    """preprocess_image (KmeanGrids.py:269-286) on (..., 3) u8 -> (..., 4) u8"""
+    img3 = np.ascontiguousarray(img3, np.uint8)
+    out = np.empty(img3.shape[:-1] + (4,), np.uint8)
+    check(load().ofc_preprocess_rgba(device, ptr(img3), img3.size // 3, thresh, ptr(out)))
+    return out
 
 
 def grid_cell_means(bgr, rows=14, cols=25, device=0):
@@ -67,4 +99,24 @@ def grid_kmeans(bgr, k=1, rows=14, cols=25, init=None, max_iter=300, tol=1e-4, c
     hsv = np.empty((nc, 3), np.uint8)
     check(load().ofc_grid_kmeans(device, ptr(bgr), W, H, rows, cols, k, ptr(init), max_iter, tol, channel_order,
                                  ptr(centers), ptr(hsv)))
+    return centers, hsv
+
+
+def grid_kmeans_frames(frames, k=1, rows=14, cols=25, init=None, max_iter=300, tol=1e-4, channel_order=0, device=0):
+    """grid_kmeans on n device-resident frames in one launch: (n, H, W, 3) u8 -> ((n, cells, 4) f64, (n, cells, 3) u8)"""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, H, W = frames.shape[:3]
+    nc = rows * cols
+    if init is not None:
+        init = np.ascontiguousarray(init, np.float64)
+        if init.shape != (n, nc, k, 4):
+            raise ValueError(f"init must be ({n}, {nc}, {k}, 4)")
+    centers = np.empty((n, nc, 4), np.float64)
+    hsv = np.empty((n, nc, 3), np.uint8)
+    src = DeviceBuffer(frames.nbytes, device).upload(frames)
+    try:
+        check(load().ofc_grid_kmeans_dev(device, src.ptr, W, H, n, rows, cols, k, ptr(init), max_iter, tol,
+                                         channel_order, ptr(centers), ptr(hsv)))
+    finally:
+        src.free()
     return centers, hsv
