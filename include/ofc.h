@@ -222,6 +222,10 @@ int ofc_lloyd_colstats_dev(int device, const void *X_dev, int dtype, int64_t N, 
  * number of labels that changed] */
 int ofc_lloyd_step_dev(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *mean,
                        const double *centers_c, uint8_t *labels_dev, int accumulate, double *record);
+/* PRECONDITION of ofc_lloyd_inertia_dev and ofc_lloyd_farthest_dev: every labels_dev[i] < k.  The kernels index
+ * centers_c + label * d without a test, so a label that is still 0xFF (unassigned) reads past the k x d centres.  Run
+ * ofc_lloyd_step_dev with the same k on the buffer first (it rewrites every label to a value below k); neither call
+ * checks this itself: the labels live on the device and a check would cost a sweep. */
 /* sum_i ||(x_i - mean) - centers_c[label_i]||^2 */
 int ofc_lloyd_inertia_dev(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *mean,
                           const double *centers_c, const uint8_t *labels_dev, double *inertia);
