@@ -59,6 +59,16 @@ int ofc_device_sync(int device);
  * Replaces cv2.calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15, 3, 5, 1.2, 0)
  * (computeOpticalFlowModule.py:20-22, computeOpticalFlow.py:99-101).
  * ------------------------------------------------------------------------------------------ */
+/* The accepted domain, all of it checked by ofc_flow_create (and so by ofc_stream_create and the Python front ends) before
+ * anything is allocated: frames 16 .. 16384 pixels a side; pyr_scale in (0, 1); levels 0 .. 16; iterations 1 .. 64; winsize
+ * odd, 5 .. OFC_WINSIZE_MAX; poly_n 5 or 7; flags 0; max_batch 1 .. 4096 (violations OFC_EINVAL, except where noted below).
+ * Two limits depend on the frame size as well, and are refused with OFC_EUNSUPPORTED and a message naming the level:
+ *  - the blur of a pyramid level has at most 31 taps.  Level k is blurred with sigma = (pyr_scale^-k - 1) / 2 over
+ *    cvRound(5 sigma) | 1 taps, so a level may shrink the frame by less than 13.6x: levels <= 3 at pyr_scale 0.5, <= 1 at
+ *    0.25, <= 2 at 0.3, <= 7 at 0.7, <= 11 at 0.8, any (<= 16) from 0.85 up; in general levels <= log(13.6) / log(1 / pyr_scale).
+ *    Only levels that are built count: cv2's rule drops a level once min(W, H) * pyr_scale^k < 32, so pyr_scale 0.5 with
+ *    levels 4 is accepted below 512 pixels a side (where it runs 3 levels or fewer) and refused from 512 x 512 on.
+ *  - with winsize <= 15 (the fused iteration), W * H * 5 < 2^30, i.e. up to about 14654 x 14654. */
 typedef struct ofc_fb_params {
     double pyr_scale;  /* 0.5 */
     int levels;        /* 3   */

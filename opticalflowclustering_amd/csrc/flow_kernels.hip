@@ -292,45 +292,67 @@ __global__ __launch_bounds__(256) void k_level_dec(const uint8_t *__restrict__ s
     }
 }
 
-int launch_level_image(const uint8_t *src, float *dst, int nimg, int W0, int H0,
-                       const LevelGeom &g, hipStream_t s)
+// What launch_level_image will do with a level, decided on the host with no launch: which of its four paths the level
+// takes (0: the 3x3 level-0 kernel, 2 / 4 / 8: exact decimation, 1: the general LDS-staged tile) and, for the general
+// path, the tile and its LDS size -- or the refusal.  launch_level_image launches exactly what this returns and
+// flow_levels_check (the walk ofc_flow_create runs before it allocates) asks it about every level, so the limits of the
+// launch and of the walk are one piece of code.
+static int level_image_plan(int W0, int H0, const LevelGeom &g, bool src_aligned, LevelArgs &a, int &path, size_t &lds)
 {
-    LevelArgs a;
     memset(&a, 0, sizeof(a));
     a.W0 = W0; a.H0 = H0; a.w = g.w; a.h = g.h;
     a.r = g.ksize / 2;
+    lds = 0;
     if (g.ksize > 31) { set_error("blur kernel size %d > 31 unsupported", g.ksize); return OFC_EUNSUPPORTED; }
     gaussian_kernel(g.ksize, g.sigma, a.kern);
     a.sx = (double)W0 / g.w; a.sy = (double)H0 / g.h;
     // fast paths: exact decimation by 1 / 2 / 4 / 8 with the reference's tap counts, rows dword-addressable
-    const bool aligned = (W0 % 4) == 0 && ((uintptr_t)src % 4) == 0 && (((size_t)W0 * H0) % 4) == 0;
-    if (aligned && g.w == W0 && g.h == H0 && a.r == 1) {
-        hipLaunchKernelGGL(k_level0, dim3(cdiv(W0, 256), cdiv(H0, 32), nimg), dim3(256), 0, s, src, dst, W0, H0,
-                           a.kern[0], a.kern[1], a.kern[2]);
-        OFC_HIP(hipGetLastError());
-        return OFC_OK;
-    }
-#define OFC_DEC(S_, R_, TX_, TY_)                                                                          \
-    if (aligned && g.w * S_ == W0 && g.h * S_ == H0 && a.r == R_ && H0 > 2 * R_ + S_ && W0 > 2 * R_ + 8) {                                        \
-        hipLaunchKernelGGL((k_level_dec<S_, R_, TX_, TY_>), dim3(cdiv(g.w, TX_), cdiv(g.h, TY_), nimg),    \
-                           dim3(256), 0, s, src, dst, W0, H0, g.w, g.h, a);                                \
-        OFC_HIP(hipGetLastError());                                                                        \
+    const bool aligned = (W0 % 4) == 0 && src_aligned && (((size_t)W0 * H0) % 4) == 0;
+    if (aligned && g.w == W0 && g.h == H0 && a.r == 1) { path = 0; return OFC_OK; }
+#define OFC_DEC(S_, R_)                                                                                    \
+    if (aligned && g.w * S_ == W0 && g.h * S_ == H0 && a.r == R_ && H0 > 2 * R_ + S_ && W0 > 2 * R_ + 8) { \
+        path = S_;                                                                                         \
         return OFC_OK;                                                                                     \
     }
-    OFC_DEC(2, 1, 64, 16)
-    OFC_DEC(4, 4, 32, 8)
-    OFC_DEC(8, 9, 32, 8)
+    OFC_DEC(2, 1)
+    OFC_DEC(4, 4)
+    OFC_DEC(8, 9)
 #undef OFC_DEC
     // general path (any scale / tap count): LDS-staged tile
+    path = 1;
     if (a.sx <= 2.5) { a.txo = 64; a.tyo = 16; } else { a.txo = 32; a.tyo = 8; }
     a.in_w = (int)(a.txo * a.sx) + 2 * a.r + 4;
     a.in_h = (int)(a.tyo * a.sy) + 2 * a.r + 4;
     a.in_pitch = (a.in_w + 3) & ~3;
-    size_t lds = (size_t)(2 * a.txo + 3 * a.tyo) * 4 + (size_t)a.in_h * 2 * a.txo * 4 +
-                 (size_t)a.in_h * a.in_pitch;
+    lds = (size_t)(2 * a.txo + 3 * a.tyo) * 4 + (size_t)a.in_h * 2 * a.txo * 4 + (size_t)a.in_h * a.in_pitch;
     if (lds > 160 * 1024) { set_error("level_image tile needs %zu B LDS", lds); return OFC_EUNSUPPORTED; }
-    dim3 grid(cdiv(g.w, a.txo), cdiv(g.h, a.tyo), nimg);
-    hipLaunchKernelGGL(k_level_image, grid, dim3(256), lds, s, src, dst, a);
+    return OFC_OK;
+}
+
+int launch_level_image(const uint8_t *src, float *dst, int nimg, int W0, int H0,
+                       const LevelGeom &g, hipStream_t s)
+{
+    LevelArgs a;
+    int path = 1;
+    size_t lds = 0;
+    OFC_TRY(level_image_plan(W0, H0, g, ((uintptr_t)src % 4) == 0, a, path, lds));
+    switch (path) {
+    case 0:
+        hipLaunchKernelGGL(k_level0, dim3(cdiv(W0, 256), cdiv(H0, 32), nimg), dim3(256), 0, s, src, dst, W0, H0,
+                           a.kern[0], a.kern[1], a.kern[2]);
+        break;
+#define OFC_DEC(S_, R_, TX_, TY_)                                                                          \
+    case S_:                                                                                               \
+        hipLaunchKernelGGL((k_level_dec<S_, R_, TX_, TY_>), dim3(cdiv(g.w, TX_), cdiv(g.h, TY_), nimg),    \
+                           dim3(256), 0, s, src, dst, W0, H0, g.w, g.h, a);                                \
+        break;
+    OFC_DEC(2, 1, 64, 16)
+    OFC_DEC(4, 4, 32, 8)
+    OFC_DEC(8, 9, 32, 8)
+#undef OFC_DEC
+    default:
+        hipLaunchKernelGGL(k_level_image, dim3(cdiv(g.w, a.txo), cdiv(g.h, a.tyo), nimg), dim3(256), lds, s, src, dst, a);
+    }
     OFC_HIP(hipGetLastError());
     return OFC_OK;
 }
@@ -1415,12 +1437,19 @@ int flow_iter_max_grid(int W, int H, int npair, int winsize)
     return cdiv(cdiv(W, 256 - (winsize - 1)) * cdiv(H, rows), 8) * 8 * npair;
 }
 
+// the limits of launch_flow_iter that depend on the level's size and the window alone (also asked by flow_levels_check)
+static int flow_iter_check(int W, int H, int winsize)
+{
+    if (winsize > 15) { set_error("fused iteration supports winsize <= 15 (ring of 16 rows)"); return OFC_EUNSUPPORTED; }
+    if ((int64_t)W * H * 5 >= (1ll << 30)) { set_error("frame too large for 32-bit R offsets (%dx%d)", W, H); return OFC_EUNSUPPORTED; }
+    return OFC_OK;
+}
+
 int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out,
                      int npair, int W, int H, int winsize, hipStream_t s, const float *coarse, int sw, int sh,
                      float mul, double *uv_sum, double *uv_scratch, size_t uv_scratch_doubles)
 {
-    if (winsize > 15) { set_error("fused iteration supports winsize <= 15 (ring of 16 rows)"); return OFC_EUNSUPPORTED; }
-    if ((int64_t)W * H * 5 >= (1ll << 30)) { set_error("frame too large for 32-bit R offsets (%dx%d)", W, H); return OFC_EUNSUPPORTED; }
+    OFC_TRY(flow_iter_check(W, H, winsize));
     const int rows_per_block = flow_iter_rows(W, H, npair, winsize);
     UpsArgs u;
     u.src = coarse; u.sw = sw; u.sh = sh; u.mul = mul;
@@ -1489,6 +1518,39 @@ int launch_flow_iter_stamped(const float *R, size_t frame_stride_R, const float 
         hipLaunchKernelGGL((k_flow_iter<7, 0, true>), grid, dim3(256), 0, s, R, frame_stride_R, flow_in, flow_out, W, H,
                            rows_per_block, u, tx, ns, npair, dbg);
     OFC_HIP(hipGetLastError());
+    return OFC_OK;
+}
+
+// The walk ofc_flow_create runs over an engine's levels before it allocates anything: every limit the launches of
+// flow_run apply that follows from the frame size and the parameters alone, asked of the same functions the launches
+// ask (level_image_plan, flow_iter_check), coarsest level first as flow_run visits them.  A refusal names the level and
+// the limit.  (Engine buffers are hipMalloc'ed, so the level images see dword-aligned frames; a level that takes a
+// decimation path when aligned also fits the general path's limits, so the answer does not depend on that.)
+int flow_levels_check(int W, int H, const ofc_fb_params &p, const LevelGeom *geom, int levels, bool fused, bool fuse_level0)
+{
+    for (int k = levels; k >= 0; k--) {
+        const LevelGeom &g = geom[k];
+        int rc = OFC_OK;
+        if (!(k == 0 && fuse_level0 && polyexp_u8_ok(W, H, g))) {
+            LevelArgs a;
+            int path;
+            size_t lds;
+            rc = level_image_plan(W, H, g, true, a, path, lds);
+        }
+        if (rc == OFC_OK && fused) rc = flow_iter_check(g.w, g.h, p.winsize);
+        if (rc == OFC_OK) continue;
+        const std::string why = ofc_last_error();
+        if (g.ksize > 31) {
+            int ok = k;         // the deepest level whose blur fits: the `levels` this pyr_scale allows at this size
+            while (ok > 0 && geom[ok].ksize > 31) ok--;
+            set_error("pyramid level %d (%dx%d, sigma %.3g) of %dx%d at pyr_scale %g: %s; levels <= %d is supported with this "
+                      "pyr_scale (a level may shrink the frame by less than 13.6x)", k, g.w, g.h, g.sigma, W, H, p.pyr_scale,
+                      why.c_str(), ok);
+        } else {
+            set_error("pyramid level %d (%dx%d) of %dx%d at pyr_scale %g: %s", k, g.w, g.h, W, H, p.pyr_scale, why.c_str());
+        }
+        return rc;
+    }
     return OFC_OK;
 }
 

@@ -411,16 +411,10 @@ int ofc_flow_create(int device, int W, int H, const ofc_fb_params *p, int max_ba
     OFC_TRY(check_params(prm, W, H));
     OFC_REQUIRE(max_batch >= 1 && max_batch <= 4096, "max_batch out of range");
     OFC_REQUIRE((prm.winsize & 1) && prm.winsize >= 5, "winsize must be odd and >= 5");
-    OFC_TRY(ensure_device(device));
     std::unique_ptr<ofc_flow> f(new ofc_flow);
     f->device = device; f->W = W; f->H = H; f->max_batch = max_batch; f->prm = prm;
     f->levels = pyramid_levels(W, H, prm);
     for (int k = 0; k <= f->levels; k++) f->geom.push_back(level_geometry(W, H, prm, k));
-    polyexp_setup(prm.poly_n, prm.poly_sigma, f->pc);
-    OFC_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
-    const size_t P0 = (size_t)W * H, nb = (size_t)max_batch;
-    OFC_TRY(f->I.alloc(sizeof(float) * P0 * (nb + 1)));
-    OFC_TRY(f->R.alloc(sizeof(float) * 5 * P0 * (nb + 1)));
     {
         const char *e = getenv("OFC_FLOW_STAGED");      // debugging aid: force the separate K4 / K5 kernels
         f->fused = prm.winsize <= 15 && !(e && e[0] == '1');
@@ -440,6 +434,16 @@ int ofc_flow_create(int device, int W, int H, const ofc_fb_params *p, int max_ba
             if (v > 1) f->fuse2_min_w = v;
         }
     }
+    // what the launches of flow_run would refuse at the first calc (a level whose blur is wider than 31 taps, a level image
+    // tile beyond the LDS, a frame beyond the fused iteration's 32-bit offsets) is refused here, before the device is
+    // touched: nothing is allocated, and the streaming forms have stored no frame
+    OFC_TRY(flow_levels_check(W, H, prm, f->geom.data(), f->levels, f->fused, f->fuse_level0));
+    OFC_TRY(ensure_device(device));
+    polyexp_setup(prm.poly_n, prm.poly_sigma, f->pc);
+    OFC_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    const size_t P0 = (size_t)W * H, nb = (size_t)max_batch;
+    OFC_TRY(f->I.alloc(sizeof(float) * P0 * (nb + 1)));
+    OFC_TRY(f->R.alloc(sizeof(float) * 5 * P0 * (nb + 1)));
     if (f->fused) {
         OFC_TRY(f->flowC.alloc(sizeof(float) * 2 * P0 * nb));
     } else {

@@ -123,6 +123,9 @@ int launch_flow_iter_pipe(const float *R, size_t frame_stride_R, const float *fl
                           size_t uv_scratch_doubles);
 int launch_flow_iter_stamped(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W,
                              int H, hipStream_t s, unsigned long long *dbg, int *grid_out);
+// every size- and parameter-dependent limit of the launches above, for all levels of an engine (geom[0..levels]), with no
+// launch and no allocation: OFC_OK, or OFC_EUNSUPPORTED with a message naming the level and the limit
+int flow_levels_check(int W, int H, const ofc_fb_params &p, const LevelGeom *geom, int levels, bool fused, bool fuse_level0);
 int polyexp_default_rows(int W, int H, int nimg);
 int box_default_rows(int W, int H, int npair);
 int box_wide_rows(int winsize);   // strip height of k_box_solve_wide

@@ -1,0 +1,296 @@
+"""The case tables test_gpu_flow_domain.py (GPU, against the oracle) and test_oracle_flow_domain.py (CPU, oracle against
+float64) share, and the inputs both build from them.  numpy only at import: the float64 restatement pulls scipy in when it
+is called, which the GPU module never does.
+
+Tile geometry restated from csrc/flow_kernels.hip: k_flow_iter<M, UPS> and k_box_solve<M> (M = winsize / 2) both give a
+256-thread work-group 256 - 2M = 256 - (winsize - 1) output columns, so the seams between work-groups fall on multiples of
+T = 257 - winsize; flow_iter_rows / box_default_rows cut the rows into strips that are multiples of 16 (box: of 4)."""
+import json
+import os
+
+import numpy as np
+
+from opticalflowclustering_amd import synth
+from oracle import oracle as O
+
+BARS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "flow_domain_bars.json")
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. stage level: fused iteration and staged box mean + solve, every window, widths on the tile seams
+# ---------------------------------------------------------------------------------------------------------------------
+ITER_WINDOWS = (5, 7, 9, 11, 13, 15)            # k_flow_iter<M, UPS>, M = 2 .. 7
+BOX_WINDOWS = (5, 7, 9, 11, 13, 15, 17)         # k_box_solve<M>, M = 2 .. 8
+ITER_COUNTS = (1, 2, 3)
+HEIGHTS = (16, 17, 31, 33, 200)                 # one strip exactly, one row more, around two strips, many strips
+
+
+def tile_width(ws):
+    return 256 - (ws - 1)
+
+
+def seam_widths(ws):
+    T = tile_width(ws)
+    return (("T-1", T - 1), ("T", T), ("T+1", T + 1), ("2T", 2 * T), ("2T+1", 2 * T + 1), ("narrow", 17))
+
+
+def stage_sizes(ws):
+    """six (name, W, H): every seam width of the window once, every height at least once (the pairing rotates with the
+    window so that no width always meets the same height)"""
+    rot = (ws // 2) % len(HEIGHTS)
+    return [(name, W, HEIGHTS[(i + rot) % len(HEIGHTS)]) for i, (name, W) in enumerate(seam_widths(ws))]
+
+
+def iter_case_id(ws, name, W, H, iters):
+    return f"iter-ws{ws}-M{ws // 2}-{name}-{W}x{H}-it{iters}"
+
+
+def box_case_id(ws, name, W, H):
+    return f"box-ws{ws}-M{ws // 2}-{name}-{W}x{H}"
+
+
+ITER_CASES = [(ws, name, W, H) for ws in ITER_WINDOWS for (name, W, H) in stage_sizes(ws)]
+BOX_CASES = [(ws, name, W, H) for ws in BOX_WINDOWS for (name, W, H) in stage_sizes(ws)]
+
+
+def iter_inputs(W, H, seed=0, dx=2.3, dy=-1.1):
+    """R0, R1, flow as test_gpu_flow._iter_case builds them"""
+    a, b = synth.translated_pair(W, H, dx, dy)
+    R0, R1 = O.polyexp(O.level_image(a, 0)), O.polyexp(O.level_image(b, 0))
+    rng = np.random.default_rng(seed)
+    flow = (rng.standard_normal((H, W, 2)) * 1.5).astype(np.float32)
+    return R0, R1, flow
+
+
+def oracle_iterations(R0, R1, flow, n, winsize):
+    """the flow after each of n iterations (oracle/farneback_ref.c's loop unrolled, as test_gpu_flow._oracle_iterations;
+    the matrices' refresh after an iteration does not touch the flow it wrote, so one pass serves every count <= n)"""
+    out = []
+    M = O.update_matrices(R0, R1, flow)
+    for i in range(n):
+        flow, M = O.update_flow_blur(R0, R1, flow, M, winsize, i < n - 1)
+        out.append(flow)
+    return out
+
+
+def f64_iterations(R0, R1, flow, n, winsize):
+    """the same iterations in float64 numpy from the same float32 inputs: warp, border attenuation, box mean and solve of
+    farneback_f64 (test_oracle_farneback_independent)"""
+    from test_oracle_farneback_independent import _solve, _update_matrices
+    R0, R1, flow = (np.asarray(a, np.float64) for a in (R0, R1, flow))
+    out = []
+    for _ in range(n):
+        flow = _solve(_update_matrices(R0, R1, flow), winsize)
+        out.append(flow)
+    return out
+
+
+def box_input(W, H):
+    """M as test_gpu_flow.test_box_solve builds it"""
+    rng = np.random.default_rng(W)
+    M = rng.random((H, W, 5)).astype(np.float32)
+    M[..., 0] += 1
+    M[..., 2] += 1
+    return M
+
+
+def oracle_box_solve(M, ws):
+    H, W = M.shape[:2]
+    z5 = np.zeros((H, W, 5), np.float32)
+    return O.update_flow_blur(z5, z5, np.zeros((H, W, 2), np.float32), M, ws, False)[0]
+
+
+def f64_box_solve(M, ws):
+    from test_oracle_farneback_independent import _solve
+    return _solve(np.asarray(M, np.float64), ws)
+
+
+# The project's own bars at winsize 15.  Iteration (test_two_iteration_kernel_against_oracle): 2e-5 * max(1, |want|) after
+# two iterations, 5e-5 after four; one iteration takes the two-iteration bar and three the four-iteration bar, because the
+# difference can only have been amplified fewer times.  Box mean + solve (test_box_solve): 1e-5 * max(1, |want|).
+def iter_base_bar(iters):
+    return 2e-5 if iters <= 2 else 5e-5
+
+
+BOX_BASE_BAR = 1e-5
+F32_FACTOR = 4          # GPU bar = max(base, 4 x the oracle's own distance from float64): FMA in the warp and exact vs
+                        # running box sums are two more float32 orderings on top of the oracle's
+CAP_FACTOR = 10         # a case whose float32-vs-float64 distance alone exceeds 10 x base is ill-conditioned: replace it
+
+
+def stage_bar(base, d64, want):
+    """(bar, cap) in pixels for one stage case: base and cap scale with max(1, |want|), the measured float64 distance
+    does not.  The cap is on d64 (test_oracle_flow_domain asserts it for every case), so the bar stays below 4 x cap"""
+    scale = max(1.0, float(np.abs(want).max()))
+    return max(base * scale, F32_FACTOR * d64), CAP_FACTOR * base * scale
+
+
+def measure_stage_distances():
+    """{case id: max |oracle - float64|} for every stage case (what make_flow_domain_bars.py records)"""
+    out = {}
+    for ws, name, W, H in ITER_CASES:
+        R0, R1, flow = iter_inputs(W, H, seed=W + ws)
+        n = max(ITER_COUNTS)
+        o32, o64 = oracle_iterations(R0, R1, flow, n, ws), f64_iterations(R0, R1, flow, n, ws)
+        for it in ITER_COUNTS:
+            out[iter_case_id(ws, name, W, H, it)] = float(np.abs(o32[it - 1] - o64[it - 1]).max())
+    for ws, name, W, H in BOX_CASES:
+        M = box_input(W, H)
+        out[box_case_id(ws, name, W, H)] = float(np.abs(oracle_box_solve(M, ws) - f64_box_solve(M, ws)).max())
+    return out
+
+
+def recorded_stage_distances():
+    with open(BARS_PATH) as f:
+        return json.load(f)["max_abs_oracle_minus_float64"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. stage level: level images at other pyramid scales.  Geometry and launch path restated from ofc_api.cpp
+#    (level_geometry, pyramid_levels) and flow_kernels.hip (level_image_plan), python's round() being cvRound's half-to-even
+# ---------------------------------------------------------------------------------------------------------------------
+def pyramid_levels(W, H, pyr_scale, levels):
+    k, scale = 0, 1.0
+    while k < levels:
+        scale *= pyr_scale
+        if W * scale < 32 or H * scale < 32:
+            break
+        k += 1
+    return k
+
+
+def level_geometry(W, H, pyr_scale, k):
+    scale = 1.0
+    for _ in range(k):
+        scale *= pyr_scale
+    sigma = (1.0 / scale - 1) * 0.5
+    ksize = max(round(sigma * 5) | 1, 3)
+    return round(W * scale), round(H * scale), ksize, sigma
+
+
+def level_path(W, H, w, h, ksize):
+    """which of launch_level_image's paths a level of a dword-aligned frame takes"""
+    r = ksize // 2
+    aligned = W % 4 == 0 and (W * H) % 4 == 0
+    if aligned and (w, h) == (W, H) and r == 1:
+        return "level0"
+    for S, R in ((2, 1), (4, 4), (8, 9)):
+        if aligned and w * S == W and h * S == H and r == R and H > 2 * R + S and W > 2 * R + 8:
+            return f"dec{S}"
+    return "general64x16" if W / w <= 2.5 else "general32x8"
+
+
+LEVEL_PATHS = ("level0", "dec2", "dec4", "dec8", "general64x16", "general32x8")
+
+# (pyr_scale, levels, W, H): levels is the deepest the 31-tap blur allows at that scale, or fewer
+LEVEL_FRAMES = [(0.5, 3, 512, 256),       # W % 4 == 0, exact x2, x4, x8: level0, dec2, dec4, dec8
+                (0.5, 3, 514, 264),       # the same decimations with W % 4 != 0: the general path at every level
+                (0.25, 1, 512, 256),      # exact x4 at level 1: dec4
+                (0.25, 1, 514, 262),      # x4, W % 4 != 0: general, 32x8 tile
+                (0.25, 1, 128, 160),      # coarsest level exactly 32 wide (dec4)
+                (0.3, 2, 400, 380),       # sx 3.33 and 11.1: general, 32x8 tile, a 25-tap blur
+                (0.7, 7, 457, 400),       # sx 1.43, 2.04 | 2.92 ...: both sides of sx = 2.5, down to 38x33
+                (0.8, 11, 500, 400),      # sx 2.44 | 3.05 at levels 4 | 5
+                (0.8, 1, 40, 50),         # coarsest level exactly 32 wide (40 * 0.8), general path
+                (0.9, 16, 322, 198)]      # all 16 levels (198 * 0.9^16 = 36.7)
+
+
+def level_cases():
+    """[(id, pyr_scale, levels, W, H, k)], one per level the pyramid reaches, the id naming the launch path"""
+    out = []
+    for ps, lv, W, H in LEVEL_FRAMES:
+        for k in range(pyramid_levels(W, H, ps, lv) + 1):
+            w, h, ksize, _ = level_geometry(W, H, ps, k)
+            out.append((f"s{ps}-{W}x{H}-k{k}-{w}x{h}-taps{ksize}-{level_path(W, H, w, h, ksize)}", ps, lv, W, H, k))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. engine level: parameters x sizes on synth.translated_pair(W, H, 1.7, -1.1)
+# ---------------------------------------------------------------------------------------------------------------------
+DEFAULTS = dict(pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2)
+ENGINE_MOTION = (1.7, -1.1)
+
+
+def _e(name, W, H, **kw):
+    return (name, dict(DEFAULTS, **kw), W, H)
+
+
+ENGINE_CASES = [
+    # every fused window (k_flow_iter<M, *>), the staged 17 and one wide window
+    _e("ws5-M2", 243, 131, winsize=5),
+    _e("ws7-M3", 243, 131, winsize=7),
+    _e("ws9-M4", 500, 300, winsize=9),
+    _e("ws11-M5", 243, 131, winsize=11),
+    _e("ws13-M6", 500, 300, winsize=13),
+    _e("ws15-M7-defaults", 243, 131),
+    _e("ws17-staged", 243, 131, winsize=17),
+    _e("ws31-wide", 243, 131, winsize=31),
+    # pyramid scales: 0.5 is the exact x2 upsample (UPS=2), every other the general taps (UPS=1); the top level is UPS=0
+    _e("scale0.3-levels2-clamped-to-1-UPS1", 500, 300, pyr_scale=0.3, levels=2),
+    _e("scale0.3-levels1-ws9-UPS1", 500, 300, pyr_scale=0.3, levels=1, winsize=9),
+    _e("scale0.5-it10-UPS2", 500, 300, iterations=10),
+    _e("scale0.7-levels6-ws11-UPS1", 500, 300, pyr_scale=0.7, levels=6, winsize=11),
+    _e("scale0.7-it10", 243, 131, pyr_scale=0.7, iterations=10),
+    _e("scale0.8-levels6-ws7-UPS1", 243, 131, pyr_scale=0.8, levels=6, winsize=7),
+    _e("scale0.9-levels16-clamped-to-13", 243, 131, pyr_scale=0.9, levels=16),
+    _e("scale0.9-it10", 500, 300, pyr_scale=0.9, iterations=10),
+    # levels
+    _e("levels0-ws9-UPS0-only", 243, 131, levels=0, winsize=9),
+    _e("levels2", 243, 131, levels=2),
+    _e("levels6-clamped-to-3", 500, 300, levels=6),
+    # one iteration per level: the launch that reads the coarser level is the only one and writes the level's result
+    _e("it1-levels1-UPS2-only-launch", 243, 131, levels=1, iterations=1),
+    _e("it1-levels2-scale0.8-ws5-UPS1-only-launch", 243, 131, pyr_scale=0.8, levels=2, iterations=1, winsize=5),
+    _e("it1-levels3-ws13", 500, 300, iterations=1, winsize=13),
+    _e("it1-ws17-staged", 243, 131, iterations=1, winsize=17),
+    # iterations
+    _e("it2-ws7", 500, 300, iterations=2, winsize=7),
+    _e("it4-ws11", 500, 300, iterations=4, winsize=11),
+    _e("it10-ws9", 243, 131, iterations=10, winsize=9),
+    _e("it64-levels1", 64, 64, iterations=64, levels=1),
+    # polynomial expansion
+    _e("poly7-sigma1.5", 243, 131, poly_n=7, poly_sigma=1.5),
+    _e("poly7-sigma1.5-scale0.7-ws9", 500, 300, poly_n=7, poly_sigma=1.5, pyr_scale=0.7, winsize=9),
+    _e("sigma1.1-ws11", 243, 131, poly_sigma=1.1, winsize=11),
+    _e("sigma1.5-ws7", 500, 300, poly_sigma=1.5, winsize=7),
+    _e("sigma0-poly5-default1.5", 243, 131, poly_sigma=0.0),
+    _e("sigma0-poly7-default2.1-ws13", 243, 131, poly_n=7, poly_sigma=0.0, winsize=13),
+    # the smallest frames
+    _e("16x16", 16, 16),
+    _e("16x16-ws5", 16, 16, winsize=5),
+    _e("16x300", 16, 300),
+    _e("16x300-ws17-staged", 16, 300, winsize=17),
+    _e("300x16-ws9", 300, 16, winsize=9),
+    # around the W * scale < 32 break
+    _e("64x64-one-level-of-32", 64, 64),
+    _e("63x65-no-level-ws7", 63, 65, winsize=7),
+    _e("65x63-no-level-ws11", 65, 63, winsize=11),
+    _e("64x64-scale0.8-three-levels-ws5", 64, 64, pyr_scale=0.8, levels=6, winsize=5),
+    _e("65x63-scale0.9-six-levels-ws13", 65, 63, pyr_scale=0.9, levels=16, winsize=13),
+    # the accepted side of the domain's edges, where it changes what is launched
+    _e("edge-scale0.99-levels16", 64, 64, pyr_scale=0.99, levels=16),
+    _e("edge-ws255", 64, 64, winsize=255),
+    _e("edge-512x512-levels3-of-scale0.5", 512, 512),                       # levels=4 is refused (39-tap blur)
+    _e("edge-640x640-levels0-of-scale0.06", 640, 640, pyr_scale=0.06, levels=0),   # levels=1 is refused
+    # one full-HD-plus-one frame: odd in both directions, eight tiles wide
+    _e("1921x1081-ws13-it2", 1921, 1081, winsize=13, iterations=2),
+]
+
+# five non-default parameter sets that also run batched (max_batch 3, on 2 and on 4 frames)
+ENGINE_BATCHED = ("ws7-M3", "scale0.7-levels6-ws11-UPS1", "it1-levels2-scale0.8-ws5-UPS1-only-launch", "ws17-staged",
+                  "poly7-sigma1.5")
+
+
+def engine_case(name):
+    return next(c for c in ENGINE_CASES if c[0] == name)
+
+
+def oracle_params(kw):
+    p = O.default_params()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def rel(a, b):
+    return np.linalg.norm((a - b).ravel().astype(np.float64)) / max(np.linalg.norm(b.ravel().astype(np.float64)), 1e-30)

@@ -51,6 +51,8 @@ def _resize_linear(a, w, h):
 def _polyexp(I, n=5, sigma=1.2):
     """per pixel, the weighted least-squares fit of b0 + b1 x + b2 y + b3 x^2 + b4 y^2 + b5 xy on the 11x11 window with
     Gaussian applicability; returns the 5 non-constant coefficients in OpenCV's storage order (y, x, y^2, x^2, xy)"""
+    if sigma < np.finfo(np.float32).eps:        # cv2's documented default for poly_sigma 0 (FarnebackPrepareGaussian)
+        sigma = n * 0.3
     x = np.arange(-n, n + 1, dtype=np.float64)
     g = np.exp(-x * x / (2 * sigma * sigma)).astype(np.float32).astype(np.float64)
     g /= g.sum()
