@@ -252,6 +252,25 @@ int ofc_lloyd_farthest_dev(int device, const void *X_dev, int dtype, int64_t N, 
  * The random draws, the cumulative sum and searchsorted stay on the host (cluster.kmeans_plusplus). */
 int ofc_kpp_candidates(int device, const void *X, int dtype, int64_t N, int d, const double *mean,
                        const int64_t *cand, int n_cand, const double *closest, double *out_min, double *pots);
+/* The whole seeding -- sklearn's _kmeans_plusplus (_kmeans.py:174-272), unit weights -- on device-resident X (this rank's
+ * shard when a communicator is active; global row order is rank order).  The caller supplies the random numbers, so the
+ * call is deterministic:
+ *   first   GLOBAL index of the first centre
+ *   u       (k-1) x n_trials uniforms in [0,1), in RandomState draw order; step c uses rand_vals = u[c-1][:] * current_pot
+ *           (may be NULL when k == 1)
+ *   colsum  this rank's column sums (as for ofc_kmeans_fit_dev_stats) or NULL
+ * centers: k x d f64 (rows of X, un-centred); indices: k GLOBAL row indices.  Same result on every rank.
+ * The running closest distances (N f64) stay in device scratch; one sweep over the samples per centre, nothing of size
+ * N crosses to the host.  The distances are k_kpp_candidates' bit for bit; the cumulative sum is formed per
+ * OFC_KPP_CHUNK samples, then per 1024 chunks, so it differs from np.cumsum's in rounding only.
+ * OFC_EINVAL: null pointers, N < 0, global N < k, first outside the global range, n_trials outside 1..8, a u outside
+ * [0,1); OFC_EUNSUPPORTED: k > 16, d > 4, more than 2^30 samples on one rank.  All checked before anything is launched. */
+int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *colsum,
+                     int64_t first, const double *u, int n_trials, double *centers, int64_t *indices);
+/* the sampling stage on its own (single rank; test and inspection hook):
+ * idx[j] = min(searchsorted(cumsum(w_dev[0..N)), r[j], side='left'), N-1), j < n <= 8, 1 <= N <= 2^30; w_dev: N f64 >= 0 */
+int ofc_kpp_sample_dev(int device, const double *w_dev, int64_t N, const double *r, int n, int64_t *idx);
+#define OFC_KPP_CHUNK 1024   /* samples per partial sum of the two-level cumulative sum */
 /* many small independent problems in one launch (the per-grid-cell shape of KmeanGrids.py:376-392):
  * problem p owns rows [offsets[p], offsets[p+1]) of X (u8, d = 4); init/centers: P x k x d f64;
  * counts: P x k i32 = np.bincount(predict(X)); labels may be NULL. */

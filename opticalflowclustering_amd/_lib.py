@@ -13,6 +13,7 @@ OFC_OK, OFC_EINVAL, OFC_ENODEV, OFC_EHIP, OFC_ENOMEM, OFC_ENOTREADY, OFC_EUNSUPP
     0, -1, -2, -3, -4, -5, -6, -7
 U8, F32, F64 = 0, 1, 2
 UNIQUE_ID_BYTES = 128
+KPP_CHUNK = 1024          # OFC_KPP_CHUNK: samples per partial sum of the seeding's two-level cumulative sum
 
 
 class OfcError(RuntimeError):
@@ -83,6 +84,8 @@ _PROTOS = {
     "ofc_lloyd_inertia_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, C.POINTER(_d)], _i),
     "ofc_lloyd_farthest_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp, _ip], _i),
     "ofc_kpp_candidates": ([_i, _vp, _i, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
+    "ofc_kpp_seed_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i, _vp, _vp], _i),
+    "ofc_kpp_sample_dev": ([_i, _vp, _i64, _vp, _i, _vp], _i),
     "ofc_kmeans_fit_batched": ([_i, _vp, _vp, _i, _i, _i, _vp, _i, _d, _vp, _vp, _vp, _vp], _i),
     "ofc_grid_kmeans": ([_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp], _i),
     "ofc_grid_kmeans_dev": ([_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp], _i),

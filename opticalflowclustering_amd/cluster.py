@@ -7,7 +7,7 @@ convergence, final E-step, empty-cluster relocation).  One deliberate difference
 constructs KMeans(n_clusters=k) with sklearn's default init='k-means++', random_state=None, i.e. a
 non-deterministic seeding.  Here `init` is an explicit (k, d) array, 'seeded-rows'
 (the default: k distinct rows of X picked by numpy's default_rng(random_state), seed 0 -- reproducible), or
-'k-means++': sklearn's own seeding (_kmeans.py:174-272) with numpy-RandomState-compatible draws, so that
+'k-means++': sklearn's own seeding (_kmeans.py:174-272, on the device: kmeans_plusplus_dev) with numpy-RandomState-compatible draws, so that
 KMeans(n_clusters=k, init='k-means++', random_state=s) lands on the centres sklearn finds for the same seed
 (random_state=None then means numpy's global RandomState, as in sklearn).  For the reference's documented k=1
 the result does not depend on the seeding at all."""
@@ -94,6 +94,51 @@ def kmeans_plusplus(X, n_clusters, random_state=None, n_local_trials=None, devic
     return X[indices].astype(np.float64), indices
 
 
+KPP_CHOICE_MAX = 1 << 24      # largest global N whose first index is drawn with rs.choice (see kpp_draws)
+
+
+def kpp_draws(rs, N, n_clusters, n_local_trials=None):
+    """every random number _kmeans_plusplus consumes, drawn up front in sklearn's order (none of them depends on the
+    data): the first index (:224), then uniform(size=n_local_trials) per further centre (:242).
+    -> (first, u (n_clusters-1, n_local_trials), n_local_trials).
+    Up to KPP_CHOICE_MAX rows the first index is sklearn's own rs.choice(N, p=uniform).  Above that it is
+    min(int(rs.random_sample() * N), N - 1): choice draws that same single random_sample() and looks it up in the
+    cumulative sum of p -- the same distribution, without three N-long float64 vectors (5 GB each for a clip)."""
+    if n_local_trials is None:
+        n_local_trials = 2 + int(np.log(n_clusters))                              # :217-221
+    if n_local_trials > 8:
+        raise ValueError("n_local_trials > 8 is not supported")
+    if N <= KPP_CHOICE_MAX:
+        weight = np.ones(N, np.float64)
+        first = int(rs.choice(N, p=weight / weight.sum()))
+    else:
+        first = min(int(rs.random_sample() * N), N - 1)
+    u = np.empty((n_clusters - 1, n_local_trials), np.float64)
+    for c in range(n_clusters - 1):
+        u[c] = rs.uniform(size=n_local_trials)
+    return first, u, n_local_trials
+
+
+def kmeans_plusplus_dev(X_ptr, dtype, N, d, n_clusters, random_state=None, n_local_trials=None, device=0,
+                        colsum=None, n_global=None):
+    """kmeans_plusplus on device-resident X (this rank's shard when a communicator is active: then n_global is the
+    row count over all ranks, and every rank passes the same random_state).  The whole seeding runs in libofc
+    (ofc_kpp_seed_dev): the closest distances stay on the device, each further centre costs one sweep over X.
+    The draws are kpp_draws'.  colsum as for kmeans_fit_dev.  -> (centres (k,d) f64 rows of X, GLOBAL indices)"""
+    n_global = int(N if n_global is None else n_global)
+    if n_global < 1:
+        raise ValueError(f"n_samples={n_global} should be >= n_clusters={n_clusters}.")
+    first, u, n_local_trials = kpp_draws(check_random_state(random_state), n_global, int(n_clusters), n_local_trials)
+    cs = np.ascontiguousarray(colsum, np.float64) if colsum is not None else None
+    if cs is not None and cs.shape != (d,):
+        raise ValueError(f"colsum must have shape ({d},)")
+    centers = np.empty((n_clusters, d), np.float64)
+    indices = np.empty(n_clusters, np.int64)
+    check(load().ofc_kpp_seed_dev(device, C.c_void_p(X_ptr), dtype, N, d, n_clusters, ptr(cs), first, ptr(u),
+                                  n_local_trials, ptr(centers), ptr(indices)))
+    return centers, indices
+
+
 class KMeans:
     def __init__(self, n_clusters=8, *, init="seeded-rows", n_init=1, max_iter=300, tol=1e-4,
                  random_state=0, device=0, **_ignored):
@@ -103,7 +148,7 @@ class KMeans:
     def _init_centers(self, X):
         if isinstance(self.init, str):
             if self.init == "k-means++":
-                return kmeans_plusplus(X, self.n_clusters, self.random_state, device=self.device)[0]
+                return None                      # fit seeds on the uploaded X
             if self.init not in ("seeded-rows", "random"):
                 raise ValueError(f"init should be an array, 'k-means++' or 'seeded-rows', got {self.init!r}")
             return seeded_rows_init(X, self.n_clusters, self.random_state if self.random_state is not None else 0)
@@ -125,8 +170,22 @@ class KMeans:
         centers = np.empty((k, d), np.float64)
         labels = np.empty(N, np.int32)
         inertia, n_iter = C.c_double(), C.c_int()
-        check(load().ofc_kmeans_fit(self.device, ptr(X), _DT[X.dtype], N, d, k, ptr(C0), self.max_iter,
-                                    self.tol, ptr(centers), ptr(labels), C.byref(inertia), C.byref(n_iter)))
+        if C0 is None:                           # 'k-means++': one upload serves the seeding and the fit
+            Xd = _lib.DeviceBuffer(X.nbytes, self.device)
+            Ld = _lib.DeviceBuffer(N, self.device)
+            try:
+                Xd.upload(X)
+                C0, _ = kmeans_plusplus_dev(Xd.ptr, _DT[X.dtype], N, d, k, self.random_state, device=self.device)
+                check(load().ofc_kmeans_fit_dev(self.device, C.c_void_p(Xd.ptr), _DT[X.dtype], N, d, k, ptr(C0),
+                                                self.max_iter, self.tol, ptr(centers), C.c_void_p(Ld.ptr),
+                                                C.byref(inertia), C.byref(n_iter)))
+                labels[:] = Ld.download((N,), np.uint8)
+            finally:
+                Xd.free()
+                Ld.free()
+        else:
+            check(load().ofc_kmeans_fit(self.device, ptr(X), _DT[X.dtype], N, d, k, ptr(C0), self.max_iter,
+                                        self.tol, ptr(centers), ptr(labels), C.byref(inertia), C.byref(n_iter)))
         self.cluster_centers_, self.labels_ = centers, labels
         self.inertia_, self.n_iter_ = inertia.value, n_iter.value
         self.n_features_in_ = d

@@ -25,6 +25,8 @@ struct LloydScratch {
     DevBuf state, partial, tot, tot_local, excl, far, labels;
     DevBuf tile_box, tile_sum, tile_sq;  // lloyd_tiles.hip: 16 + 16 + 8 B per 64-sample tile, rebuilt by every fit (k_tile_meta)
     DevBuf tile_meta;                    // k_tile_meta's reduced record (4 doubles)
+    DevBuf kpp_closest, kpp_cs, kpp_ss;  // lloyd_seed.hip: closest[N], chunk sums [8][N / OFC_KPP_CHUNK], their sums per 1024
+    DevBuf kpp_io;                       // seeding: [8 indices | 8 x LLOYD_DMAX rows | 192 doubles of all-reduce staging]
     double prune_stats[6] = {0, 0, 0, 0, 0, 0};   // of the last fit, see ofc_lloyd_prune_stats
     LloydStatus *status = nullptr;       // pinned, device-visible; one slot per iteration of a window
     LloydStatus *status_dev = nullptr;
@@ -657,6 +659,228 @@ int ofc_kpp_candidates(int device, const void *X, int dtype, int64_t N, int d, c
     OFC_HIP(hipMemcpy(t, tot.p, sizeof(t), hipMemcpyDeviceToHost));
     for (int c = 0; c < n_cand; c++) pots[c] = t[c];
     OFC_HIP(hipMemcpy(out_min, out.p, sizeof(double) * (size_t)N * n_cand, hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+/* ---- k-means++ seeding on resident samples, see include/ofc.h and lloyd_seed.hip ---- */
+namespace {
+constexpr int KPP_IO_ROWS = 8, KPP_IO_STAGE = 8 + 8 * LLOYD_DMAX, KPP_IO_LEN = KPP_IO_STAGE + 192;
+
+// all-reduce of a few host doubles through the seeding scratch (no-op without a communicator)
+int kpp_exchange(LloydScratch &sc, double *h, int count, int op)
+{
+    if (!dist_active()) return OFC_OK;
+    double *dv = sc.kpp_io.as<double>() + KPP_IO_STAGE;
+    OFC_HIP(hipMemcpyAsync(dv, h, sizeof(double) * count, hipMemcpyHostToDevice, sc.stream));
+    OFC_TRY(dist_allreduce_f64(dv, count, op, sc.stream));
+    OFC_HIP(hipMemcpyAsync(h, dv, sizeof(double) * count, hipMemcpyDeviceToHost, sc.stream));
+    OFC_HIP(hipStreamSynchronize(sc.stream));
+    return OFC_OK;
+}
+
+// potentials of the candidates the last sweep evaluated (this rank's share)
+int kpp_local_pots(LloydScratch &sc, int nblocks, double *pots8)
+{
+    OFC_TRY(launch_reduce_records(sc.partial.as<double>(), nblocks, 8, sc.tot.as<double>(), sc.stream));
+    OFC_HIP(hipMemcpyAsync(pots8, sc.tot.p, sizeof(double) * 8, hipMemcpyDeviceToHost, sc.stream));
+    OFC_HIP(hipStreamSynchronize(sc.stream));
+    return OFC_OK;
+}
+}  // namespace
+
+int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *colsum,
+                     int64_t first, const double *u, int n_trials, double *centers, int64_t *indices)
+{
+    OFC_REQUIRE(X_dev && centers && indices && (u || k == 1), "null pointer");
+    OFC_REQUIRE(dtype >= OFC_U8 && dtype <= OFC_F64, "bad dtype %d", dtype);
+    OFC_REQUIRE(N >= 0, "N=%lld is negative", (long long)N);
+    OFC_TRY(check_kd(k, d));
+    OFC_REQUIRE(n_trials >= 1 && n_trials <= 8, "n_trials %d outside 1..8", n_trials);
+    for (int i = 0; i < (k - 1) * n_trials; i++)
+        OFC_REQUIRE(u[i] >= 0.0 && u[i] < 1.0, "u[%d]=%g outside [0,1)", i, u[i]);
+    OFC_REQUIRE(first >= 0, "first=%lld is negative", (long long)first);
+    if (N > KPP_NMAX) {
+        set_error("N=%lld outside the seeding kernels' range (<= %lld samples per rank)", (long long)N, (long long)KPP_NMAX);
+        return OFC_EUNSUPPORTED;
+    }
+    const int world = dist_active() ? dist_world() : 1, rank = dist_active() ? dist_rank() : 0;
+    if (world > 64) { set_error("seeding over %d ranks is not supported (<= 64)", world); return OFC_EUNSUPPORTED; }
+    if (world == 1) {       // with a communicator the same two tests follow the exchange of the shard sizes
+        OFC_REQUIRE(N >= k, "n_samples=%lld should be >= n_clusters=%d.", (long long)N, k);
+        OFC_REQUIRE(first < N, "first=%lld outside 0..%lld", (long long)first, (long long)N - 1);
+    }
+    OFC_TRY(ensure_device(device));
+    LloydScratch &sc = scratch_for(device);
+    std::lock_guard<std::mutex> lock(sc.mu);
+    OFC_TRY(sc.init());
+    hipStream_t s = sc.stream;
+    if (!sc.kpp_io.p) OFC_TRY(sc.kpp_io.alloc(sizeof(double) * KPP_IO_LEN));
+    int64_t *idx_dev = sc.kpp_io.as<int64_t>();
+    double *rows_dev = sc.kpp_io.as<double>() + KPP_IO_ROWS;
+
+    // ---- shard layout: global row order is rank order ----
+    std::vector<double> nq(world, 0.0), pq(world, 0.0);
+    nq[rank] = (double)N;
+    OFC_TRY(kpp_exchange(sc, nq.data(), world, DIST_SUM));
+    double Ng = 0, off_me = 0;
+    for (int q = 0; q < world; q++) {
+        if (q < rank) off_me += nq[q];
+        Ng += nq[q];
+    }
+    OFC_REQUIRE(Ng >= (double)k, "n_samples=%.0f should be >= n_clusters=%d.", Ng, k);
+    OFC_REQUIRE((double)first < Ng, "first=%lld outside 0..%.0f", (long long)first, Ng - 1);
+    if (nq[rank] != (double)N) { set_error("the communicator does not lay the shards out by rank"); return OFC_EUNSUPPORTED; }
+
+    // ---- column mean, as the fit forms it ----
+    double *tot = sc.tot.as<double>();
+    double hbuf[LLOYD_DMAX], mean_h[LLOYD_DMAX];
+    const int nb_stats = lloyd_grid(N);
+    if (colsum) {
+        memcpy(hbuf, colsum, sizeof(double) * d);
+    } else {
+        LloydState *st = sc.state.as<LloydState>();
+        OFC_TRY(launch_lloyd_colstats(X_dev, dtype, N, d, st->mean, 0, sc.partial.as<double>(), nb_stats, s));
+        OFC_TRY(launch_reduce_records(sc.partial.as<double>(), nb_stats, d, tot, s));
+        OFC_HIP(hipMemcpyAsync(hbuf, tot, sizeof(double) * d, hipMemcpyDeviceToHost, s));
+        OFC_HIP(hipStreamSynchronize(s));
+    }
+    OFC_TRY(kpp_exchange(sc, hbuf, d, DIST_SUM));
+    for (int f = 0; f < d; f++) mean_h[f] = hbuf[f] / Ng;
+
+    const int64_t nchunks = kpp_chunks(N);
+    const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(nchunks, 4), 2048));
+    if (N > 0) {
+        if (sc.kpp_closest.bytes < sizeof(double) * (size_t)N) OFC_TRY(sc.kpp_closest.alloc(sizeof(double) * (size_t)N));
+        if (sc.kpp_cs.bytes < sizeof(double) * 8 * (size_t)nchunks) {
+            OFC_TRY(sc.kpp_cs.alloc(sizeof(double) * 8 * (size_t)nchunks));
+            OFC_TRY(sc.kpp_ss.alloc(sizeof(double) * (size_t)cdiv64(nchunks, 1024)));
+        }
+    }
+    double *closest = sc.kpp_closest.as<double>(), *cs = sc.kpp_cs.as<double>(), *ss = sc.kpp_ss.as<double>();
+    const size_t es = dtype_size(dtype);
+    auto as_double = [&](const unsigned char *raw, int f) {
+        return dtype == OFC_U8 ? (double)raw[f] : dtype == OFC_F32 ? (double)((const float *)raw)[f] : ((const double *)raw)[f];
+    };
+
+    // ---- first centre: its owner broadcasts the row ----
+    double rec[8 * (LLOYD_DMAX + 1)];
+    memset(rec, 0, sizeof(rec));
+    if ((double)first >= off_me && (double)first < off_me + (double)N) {
+        unsigned char raw[LLOYD_DMAX * 8];
+        const int64_t li = first - (int64_t)off_me;
+        OFC_HIP(hipMemcpyAsync(raw, (const char *)X_dev + (size_t)li * d * es, d * es, hipMemcpyDeviceToHost, s));
+        OFC_HIP(hipStreamSynchronize(s));
+        for (int f = 0; f < d; f++) rec[f] = as_double(raw, f);
+    }
+    OFC_TRY(kpp_exchange(sc, rec, d, DIST_BCAST));
+    double prev[LLOYD_DMAX], pl[8], pg[8];
+    for (int f = 0; f < d; f++) {
+        centers[f] = rec[f];
+        prev[f] = rec[f] - mean_h[f];
+    }
+    indices[0] = first;
+    for (double &v : pl) v = 0;
+    if (N > 0) {
+        OFC_TRY(launch_kpp_sweep(X_dev, dtype, N, d, mean_h, prev, KPP_PREV_FIRST, nullptr, 0, closest, cs,
+                                 sc.partial.as<double>(), nblocks, s));
+        OFC_TRY(launch_kpp_sum1024(cs, nchunks, ss, s));
+        OFC_TRY(kpp_local_pots(sc, nblocks, pl));
+    }
+    memcpy(pg, pl, sizeof(pg));
+    OFC_TRY(kpp_exchange(sc, pg, 8, DIST_SUM));
+    double current_pot = pg[0], pot_local = pl[0];
+    int slot = 0;                 // whose chunk sums (cs[slot], summed into ss) describe closest with `prev` folded in
+
+    for (int c = 1; c < k; c++) {
+        // ---- sample n_trials rows from the cumulative sum of closest (_kmeans.py:242-247) ----
+        double r[8];
+        for (int j = 0; j < n_trials; j++) r[j] = u[(size_t)(c - 1) * n_trials + j] * current_pot;
+        for (double &v : pq) v = 0;
+        pq[rank] = pot_local;
+        OFC_TRY(kpp_exchange(sc, pq.data(), world, DIST_SUM));
+        double base_me = 0;
+        for (int q = 0; q < rank; q++) base_me += pq[q];
+        bool mine[8], any = false;
+        for (int j = 0; j < n_trials; j++) {
+            // the first non-empty shard whose cumulative sum reaches r[j]; the last non-empty one when none does (clip)
+            int owner = -1;
+            double S = 0;
+            for (int q = 0; q < world; q++) {
+                if (nq[q] > 0) {
+                    owner = q;
+                    if (S + pq[q] >= r[j]) break;
+                }
+                S += pq[q];
+            }
+            mine[j] = owner == rank;
+            any = any || mine[j];
+        }
+        memset(rec, 0, sizeof(rec));
+        if (any) {
+            int64_t idx_h[8];
+            double rows_h[8 * LLOYD_DMAX];
+            OFC_TRY(launch_kpp_sample(X_dev, dtype, N, d, mean_h, prev, c >= 2 ? KPP_PREV_APPLY : KPP_PREV_NONE, closest,
+                                      cs + (size_t)slot * nchunks, ss, r, n_trials, base_me, idx_dev, rows_dev, s));
+            OFC_HIP(hipMemcpyAsync(idx_h, idx_dev, sizeof(int64_t) * n_trials, hipMemcpyDeviceToHost, s));
+            OFC_HIP(hipMemcpyAsync(rows_h, rows_dev, sizeof(double) * n_trials * LLOYD_DMAX, hipMemcpyDeviceToHost, s));
+            OFC_HIP(hipStreamSynchronize(s));
+            for (int j = 0; j < n_trials; j++) {
+                if (!mine[j]) continue;
+                for (int f = 0; f < d; f++) rec[j * (d + 1) + f] = rows_h[j * LLOYD_DMAX + f];
+                rec[j * (d + 1) + d] = off_me + (double)idx_h[j];
+            }
+        }
+        OFC_TRY(kpp_exchange(sc, rec, n_trials * (d + 1), DIST_BCAST));
+        double cand[8 * LLOYD_DMAX];
+        for (int j = 0; j < n_trials; j++)
+            for (int f = 0; f < d; f++) cand[j * d + f] = rec[j * (d + 1) + f] - mean_h[f];
+
+        // ---- one sweep: fold the previous winner into closest, evaluate the candidates (:250-256) ----
+        for (double &v : pl) v = 0;
+        if (N > 0) {
+            OFC_TRY(launch_kpp_sweep(X_dev, dtype, N, d, mean_h, prev, c >= 2 ? KPP_PREV_APPLY : KPP_PREV_NONE, cand,
+                                     n_trials, closest, cs, sc.partial.as<double>(), nblocks, s));
+            OFC_TRY(kpp_local_pots(sc, nblocks, pl));
+        }
+        memcpy(pg, pl, sizeof(pg));
+        OFC_TRY(kpp_exchange(sc, pg, 8, DIST_SUM));
+        int best = 0;                                    // np.argmin: the first minimum (:259)
+        for (int j = 1; j < n_trials; j++)
+            if (pg[j] < pg[best]) best = j;
+        current_pot = pg[best];
+        pot_local = pl[best];
+        slot = best;
+        if (N > 0 && c + 1 < k) OFC_TRY(launch_kpp_sum1024(cs + (size_t)slot * nchunks, nchunks, ss, s));
+        for (int f = 0; f < d; f++) {
+            centers[c * d + f] = rec[best * (d + 1) + f];
+            prev[f] = cand[best * d + f];
+        }
+        indices[c] = (int64_t)rec[best * (d + 1) + d];
+    }
+    OFC_HIP(hipStreamSynchronize(s));
+    return OFC_OK;
+}
+
+int ofc_kpp_sample_dev(int device, const double *w_dev, int64_t N, const double *r, int n, int64_t *idx)
+{
+    OFC_REQUIRE(w_dev && r && idx, "null pointer");
+    OFC_REQUIRE(n >= 1 && n <= 8, "n %d outside 1..8", n);
+    OFC_REQUIRE(N >= 1, "N=%lld: nothing to sample from", (long long)N);
+    if (N > KPP_NMAX) {
+        set_error("N=%lld outside the seeding kernels' range (<= %lld samples)", (long long)N, (long long)KPP_NMAX);
+        return OFC_EUNSUPPORTED;
+    }
+    OFC_TRY(ensure_device(device));
+    const int64_t nchunks = kpp_chunks(N);
+    DevBuf cs, ss, out;
+    OFC_TRY(cs.alloc(sizeof(double) * (size_t)nchunks));
+    OFC_TRY(ss.alloc(sizeof(double) * (size_t)cdiv64(nchunks, 1024)));
+    OFC_TRY(out.alloc(sizeof(int64_t) * 8));
+    OFC_TRY(launch_kpp_sum1024(w_dev, N, cs.as<double>(), nullptr));
+    OFC_TRY(launch_kpp_sum1024(cs.as<double>(), nchunks, ss.as<double>(), nullptr));
+    OFC_TRY(launch_kpp_sample(nullptr, OFC_F64, N, 1, nullptr, nullptr, KPP_PREV_NONE, w_dev, cs.as<double>(), ss.as<double>(),
+                              r, n, 0.0, out.as<int64_t>(), nullptr, nullptr));
+    OFC_HIP(hipMemcpy(idx, out.p, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
     return OFC_OK;
 }
 

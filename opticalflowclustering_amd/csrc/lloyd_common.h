@@ -86,6 +86,25 @@ int launch_lloyd_farthest(const void *X, int dtype, int64_t N, int d, const Lloy
 int launch_kpp_candidates(const void *X, int dtype, int64_t N, int d, const double *mean, const double *cand_centred,
                           int n_cand, const double *closest, double *out, double *partial, int nblocks, hipStream_t s);
 
+// k-means++ seeding on resident samples (lloyd_seed.hip).  closest[N] f64 lives on the device; how a kernel sees it:
+enum { KPP_PREV_NONE = 0,     // as stored
+       KPP_PREV_APPLY = 1,    // min(stored, d(x, prev)): the previous step's winner is folded in (the sweep stores that)
+       KPP_PREV_FIRST = 2 };  // d(x, prev): nothing stored yet, prev is the first centre (the sweep stores that)
+constexpr int64_t KPP_NMAX = 1ll << 30;      // samples per rank: k_kpp_sample scans <= 1024 sums of 1024 chunk sums
+inline int64_t kpp_chunks(int64_t N) { return (N + OFC_KPP_CHUNK - 1) / OFC_KPP_CHUNK; }
+// one seeding step's sweep: cs[c][kpp_chunks(N)] = per-chunk sums of min(closest, d(x, cand c)) for c < max(n_cand, 1)
+// (n_cand == 0: of closest itself, slot 0), partial[block][8] = potential shares.  mean, prev, cand_centred: host
+int launch_kpp_sweep(const void *X, int dtype, int64_t N, int d, const double *mean, const double *prev, int prev_mode,
+                     const double *cand_centred, int n_cand, double *closest, double *cs, double *partial, int nblocks,
+                     hipStream_t s);
+int launch_kpp_sum1024(const double *in, int64_t n, double *out, hipStream_t s);     // out[b] = sum in[1024 b ..)
+// idx[j] = min(smallest i with base + cumsum(closest)[i] >= r[j], N - 1), rows[j][LLOYD_DMAX] = X[idx[j]], j < n <= 8;
+// cs = launch_kpp_sweep's chunk sums of that closest, ss = launch_kpp_sum1024 of cs.  X == nullptr: closest is a plain
+// weight vector (prev_mode NONE, no rows).  1 <= N <= KPP_NMAX
+int launch_kpp_sample(const void *X, int dtype, int64_t N, int d, const double *mean, const double *prev, int prev_mode,
+                      const double *closest, const double *cs, const double *ss, const double *r, int n, double base,
+                      int64_t *idx, double *rows, hipStream_t s);
+
 // distributed plumbing (dist.cpp): no-ops when no communicator is set up
 bool dist_active();
 int dist_rank();

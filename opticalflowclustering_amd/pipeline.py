@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DeviceBuffer, FbParams, check, load
-from .cluster import kmeans_fit_dev
+from .cluster import kmeans_fit_dev, kmeans_plusplus_dev
 from .flow import FlowEngine
 
 
@@ -81,9 +81,11 @@ class ClipPipeline:
         for e in self.engines:
             e.sync()
 
-    def run_kmeans(self, init, max_iter=300, tol=1e-4):
+    def run_kmeans(self, init, max_iter=300, tol=1e-4, k=None, random_state=None, n_global=None):
         """Lloyd over all local (u,v) vectors (global when a communicator is active).
-        -> centers (k,2), inertia, n_iter"""
+        init: (k,2) array, or 'k-means++' with k= and random_state=: sklearn's seeding on the resident vectors
+        (cluster.kmeans_plusplus_dev).  Under a communicator every rank passes the same random_state, and n_global = the
+        number of (u,v) vectors over all ranks.  -> centers (k,2), inertia, n_iter"""
         self.sync()
         N = self.n_pairs * self.W * self.H
         colsum = None
@@ -92,6 +94,11 @@ class ClipPipeline:
             colsum = np.zeros(2)
             for b in range(self.n_batches):                 # fixed order
                 colsum += per_batch[b]
+        if isinstance(init, str):
+            if init != "k-means++" or k is None:
+                raise ValueError(f"init should be a (k,2) array or 'k-means++' together with k=, got {init!r}, k={k!r}")
+            init, _ = kmeans_plusplus_dev(self.flows.ptr, _lib.F32, N, 2, int(k), random_state, device=self.device,
+                                          colsum=colsum, n_global=n_global)
         return kmeans_fit_dev(self.flows.ptr, _lib.F32, N, 2, init, max_iter, tol, self.labels.ptr, self.device, colsum=colsum)
 
     def sample_uv(self, idx):
