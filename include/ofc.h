@@ -110,13 +110,18 @@ int ofc_flow_calc_frames_dev_stats(ofc_flow_t *f, const uint8_t *frames_dev, int
 int ofc_flow_sync(ofc_flow_t *f);
 
 /* streaming form of ComputeOpticalFLow (computeOpticalFlowModule.py:6-36): keeps the previous
- * frame; the first push returns OFC_ENOTREADY and writes nothing. */
+ * frame; the first push returns OFC_ENOTREADY and writes nothing.
+ * An engine keeps ONE previous frame (grey, on the device), shared by ofc_flow_push_gray and ofc_flow_push_bgr: the two may
+ * be mixed, each push pairs with the frame the push before it left, whichever form that was.  A push that is refused
+ * (NULL flow_out after the first frame: OFC_EINVAL, checked before anything is copied) leaves the kept frame as it was.
+ * ofc_flow_calc and ofc_flow_calc_frames_dev[_stats] neither read nor replace it. */
 int ofc_flow_push_gray(ofc_flow_t *f, const uint8_t *gray, float *flow_out);
 
 /* ComputeOpticalFLow.compute (computeOpticalFlowModule.py:18-36) in one call: BGR frame (host) ->
  * BGR2GRAY on the device -> flow against the previous frame -> HSV-coded BGR visualisation.  The first
  * push stores the frame and returns OFC_ENOTREADY.  vis_out (HxWx3 u8), mean_mag, flow_out (HxWx2 f32)
- * may each be NULL.  The visualisation also stays resident: ofc_flow_last_vis_dev(). */
+ * may each be NULL.  The visualisation also stays resident: ofc_flow_last_vis_dev() gives its device
+ * address (HxWx3 u8, valid until the next push or ofc_flow_destroy); OFC_EINVAL until a BGR push has returned OFC_OK. */
 int ofc_flow_push_bgr(ofc_flow_t *f, const uint8_t *bgr, uint8_t *vis_out, float *mean_mag,
                       float *flow_out);
 int ofc_flow_last_vis_dev(ofc_flow_t *f, const uint8_t **vis_dev);
@@ -323,9 +328,17 @@ int ofc_dist_finalize(void);
 typedef struct ofc_stream ofc_stream_t;
 int ofc_stream_create(int device, int W, int H, const ofc_fb_params *p, int batch_pairs, int rows, int cols,
                       ofc_stream_t **out);
-/* push one HxW u8 frame; *pairs_done = pairs whose cell means are complete so far (may lag the pushes) */
+/* push one HxW u8 frame; *pairs_done (may be NULL) = pairs whose cell means are complete so far: never decreasing between
+ * two calls of ofc_stream_finish, never more than the pairs of the batches submitted (batch_pairs * ((pushes - 1) /
+ * batch_pairs)), and it may lag them */
 int ofc_stream_push_gray(ofc_stream_t *s, const uint8_t *gray, int *pairs_done);
-/* flush the partial batch, wait, and copy all cell means out: cell_uv[n_pairs][rows*cols][2] f32 */
+/* flush the partial batch, wait, and copy all cell means out: cell_uv[n_pairs][rows*cols][2] f32, *n_pairs = pushes - 1 (0
+ * after one push or none: not an error, nothing is written).  The stream is then empty and ready for the frames of another
+ * clip: no frame is carried over, the first pair of the next clip is (its frame 0, its frame 1).
+ * cell_uv too small (max_pairs < *n_pairs): OFC_EINVAL, *n_pairs is set to the number of pairs to make room for, nothing is
+ * written to cell_uv, and the results STAY with the stream: the same call with enough room returns all of them (call it again
+ * before pushing further frames).
+ * cell_uv == NULL: count only; *n_pairs is set and the results are dropped. */
 int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pairs);
 void ofc_stream_destroy(ofc_stream_t *s);
 /* per-cell mean of a flow field (host buffers): flow HxWx2 f32 -> cell_uv rows*cols x 2 f32 */

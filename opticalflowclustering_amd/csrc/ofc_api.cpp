@@ -236,6 +236,7 @@ struct ofc_flow {
     DevBuf prev_gray;               // streaming state
     bool have_prev = false;
     DevBuf bgr_in, vis, vis_partial, vis_stats, mean_mag;   // ofc_flow_push_bgr
+    bool have_vis = false;          // `vis` holds a visualisation (allocated by the first BGR push, drawn by the first pair)
     DevBuf uv_scratch;              // per-work-group (sum u, sum v) records of the last level-0 iteration (ofc_flow_calc_frames_dev_stats)
     // A batch's launch sequence (4 pyramid levels x {level image, expansion, 3 iterations}: ~20 dependent launches, most of
     // them a few microseconds long on the coarse levels) is captured once per distinct argument set into a HIP graph and
@@ -308,8 +309,9 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
                         // the field's column sums ride in the epilogue of the iteration that writes it
                         const size_t need = (size_t)flow_iter_max_grid(g.w, g.h, npair, f->prm.winsize) * 2;
                         if (f->uv_scratch.bytes < need * sizeof(double)) OFC_TRY(f->uv_scratch.alloc(need * sizeof(double)));
+                        // the launch is told what the buffer holds, not what this call needs: its own check then guards the records
                         OFC_TRY(launch_flow_iter(R, strideR, cur, nxt, npair, g.w, g.h, f->prm.winsize, s, nullptr, 0, 0, 1.f,
-                                                 uv_sum_dev, f->uv_scratch.as<double>(), need));
+                                                 uv_sum_dev, f->uv_scratch.as<double>(), f->uv_scratch.bytes / sizeof(double)));
                         uv_sum_dev = nullptr;
                     } else
                     if (plan[l] == 2) OFC_TRY(launch_flow_iter2(R, strideR, cur, nxt, npair, g.w, g.h, f->prm.winsize, s));
@@ -340,8 +342,9 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
     if (uv_sum_dev) {       // no epilogue carried them (one iteration per level, staged mode, another winsize, one of the
                             // experimental engines): one sweep over the finished field gives the same two sums
         const int64_t N = (int64_t)npair * W * H;
-        const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(N / 4, 256), 1024));
-        if (f->uv_scratch.bytes < sizeof(double) * 2 * nblocks) OFC_TRY(f->uv_scratch.alloc(sizeof(double) * 2 * nblocks));
+        const int max_blocks = 1024;    // the scratch is sized for the most records a sweep writes (16 KiB), whatever this call needs
+        const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(N / 4, 256), max_blocks));
+        if (f->uv_scratch.bytes < sizeof(double) * 2 * max_blocks) OFC_TRY(f->uv_scratch.alloc(sizeof(double) * 2 * max_blocks));
         OFC_TRY(launch_lloyd_colstats(flow_dev, OFC_F32, N, 2, nullptr, 0, f->uv_scratch.as<double>(), nblocks, s));
         OFC_TRY(launch_reduce_records(f->uv_scratch.as<double>(), nblocks, 2, uv_sum_dev, s));
     }
@@ -571,13 +574,14 @@ int ofc_flow_push_bgr(ofc_flow_t *f, const uint8_t *bgr, uint8_t *vis_out, float
     if (mean_mag) OFC_HIP(hipMemcpyAsync(mean_mag, f->mean_mag.p, sizeof(float), hipMemcpyDeviceToHost, s));
     if (flow_out) OFC_HIP(hipMemcpyAsync(flow_out, f->flow1.p, sizeof(float) * 2 * P0, hipMemcpyDeviceToHost, s));
     OFC_HIP(hipStreamSynchronize(s));
+    f->have_vis = true;
     return OFC_OK;
 }
 
 int ofc_flow_last_vis_dev(ofc_flow_t *f, const uint8_t **vis_dev)
 {
     OFC_REQUIRE(f && vis_dev, "null pointer");
-    OFC_REQUIRE(f->vis.p, "no visualisation yet: call ofc_flow_push_bgr twice first");
+    OFC_REQUIRE(f->have_vis, "no visualisation yet: no ofc_flow_push_bgr has returned OFC_OK");
     *vis_dev = f->vis.as<uint8_t>();
     return OFC_OK;
 }
