@@ -223,8 +223,9 @@ def kmeans_fit_dev(X_ptr, dtype, N, d, init, max_iter=300, tol=1e-4, labels_ptr=
 
 def prune_stats(device=0):
     """how the last kmeans_fit_dev on `device` swept its samples (ofc_lloyd_prune_stats): tile sweeps, how many of them
-    pruned, and the share of tiles the pruned sweeps did not have to read"""
+    pruned, how many counting-only (probe), the tiles the pruned sweeps tested and skipped in all, and their share"""
     out = np.zeros(6, np.float64)
     check(load().ofc_lloyd_prune_stats(device, ptr(out)))
     return {"tile_sweeps": int(out[0]), "pruned_sweeps": int(out[1]), "probe_sweeps": int(out[4]), "final_pruned": bool(out[5]),
+            "tiles_tested": int(out[2]), "tiles_pure": int(out[3]),
             "skip_fraction": float(out[3] / out[2]) if out[2] > 0 else 0.0}
