@@ -250,6 +250,60 @@ int ofc_lloyd_farthest_dev(int device, const void *X_dev, int dtype, int64_t N, 
                            const double *centers_c, const uint8_t *labels_dev, const int64_t *excl, int n_excl,
                            double *dist2, int64_t *index, double *x_c, int *label);
 
+/* ---- sample weights: KMeans(...).fit(X, sample_weight=w) (scikit-learn 1.7.2) ----
+ * What the weights change, and what they do not:
+ *   centring and tol   unweighted: X.mean(axis=0), mean(var(X)) * tol over the row count (_kmeans.py:1479-1484, _tolerance
+ *                      :279-287)
+ *   E-step             unweighted (first strict minimum of the expanded distance)
+ *   M-step             sums[label] += x_c * w (product rounded, then added), weight_in_clusters[label] += w
+ *                      (_k_means_lloyd.pyx)
+ *   empty cluster      weight_in_clusters[j] == 0: a cluster that owns only zero-weight samples is empty
+ *                      (_k_means_common.pyx:165-210); relocation picks the farthest samples by UNWEIGHTED squared distance
+ *                      and moves each with its weight: sums[old] -= x*w, sums[new] = x*w, wk[new] = w, wk[old] -= w
+ *   average            wk[j] > 0: sums / wk, otherwise the heaviest cluster's centre (_average_centers)
+ *   stop               strict label equality, else shift <= tol (_kmeans.py:716-728)
+ *   inertia            sum_i w_i |x_i - c_label|^2 (_inertia_dense, _k_means_common.pyx:128-164)
+ * w_dtype is OFC_F32 or OFC_F64 (anything else: OFC_EINVAL); the arithmetic is f64 either way.  Weighted fits read every
+ * sample in every iteration (the tile sweeps of ofc_lloyd_prune_stats hold unweighted sums).
+ * PRECONDITION of every *_dev* form: the weights are finite and >= 0, and w_dev is 16-byte aligned.  The device forms do
+ * not look (a check would cost a sweep); the host forms check on the host and return OFC_EINVAL. */
+/* ofc_kmeans_fit with host weights w[N].  OFC_EINVAL also when the weights sum to 0. */
+int ofc_kmeans_fit_w(int device, const void *X, int dtype, const void *w, int w_dtype, int64_t N, int d, int k,
+                     const double *init, int max_iter, double tol_rel, double *centers, int32_t *labels,
+                     double *inertia, int *n_iter);
+/* ofc_kmeans_fit_dev_stats with device weights w_dev[N] (this rank's shard under a communicator).  w_dev == NULL is
+ * ofc_kmeans_fit_dev_stats itself, tile sweeps included.  If the weights of all ranks sum to 0: OFC_EINVAL ("sum of sample
+ * weights must be positive"), on every rank, after iteration 0's sweep. */
+int ofc_kmeans_fit_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d,
+                         int k, const double *init, int max_iter, double tol_rel, const double *colsum,
+                         double *centers, uint8_t *labels_dev, double *inertia, int *n_iter);
+/* KMeans.score's magnitude: one E-step of the UNCENTRED host X against `centers` and sum_i w_i |x_i - c_label|^2
+ * (_labels_inertia, _kmeans.py:755-812); w may be NULL (unit weights).  score = -*inertia. */
+int ofc_kmeans_score(int device, const void *X, int dtype, const void *w, int w_dtype, int64_t N, int d, int k,
+                     const double *centers, double *inertia);
+/* ofc_lloyd_step_dev (accumulate = 1) with weights: record = [k*d sums of (x-mean)*w | k weight sums | number of labels
+ * that changed] (_k_means_lloyd.pyx's update_chunk) */
+int ofc_lloyd_step_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d,
+                         int k, const double *mean, const double *centers_c, uint8_t *labels_dev, double *record);
+/* sum_i w_i ||(x_i - mean) - centers_c[label_i]||^2 (_k_means_common.pyx:128-164); labels as for ofc_lloyd_inertia_dev */
+int ofc_lloyd_inertia_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d,
+                            int k, const double *mean, const double *centers_c, const uint8_t *labels_dev,
+                            double *inertia);
+/* ofc_lloyd_farthest_dev, which ignores the weights (_k_means_common.pyx:186-187), plus *weight = the winner's weight
+ * (:202; 0 if there is none) */
+int ofc_lloyd_farthest_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d,
+                             int k, const double *mean, const double *centers_c, const uint8_t *labels_dev,
+                             const int64_t *excl, int n_excl, double *dist2, int64_t *index, double *x_c, int *label,
+                             double *weight);
+/* Weights from a resident (u,v) field (n vectors, f32) into w_dev (n f32), every operation rounded to f32 on its own:
+ * kind 0 "magnitude": sqrtf(u*u + v*v); kind 1 "moving": u*u + v*v >= thr*thr ? 1 : 0 (thr finite, >= 0).  No reference
+ * counterpart: it serves fits that should describe the motion and not the static background. */
+int ofc_flow_weights_dev(int device, const float *flow_dev, int64_t n, int kind, float thr, float *w_dev);
+/* Measurement hook: ofc_bench_lloyd_sweep(what = 0) with a weight stream (the label-less weighted sweep, 12 B/sample with
+ * f32 weights, 16 B with f64); k 1..16 */
+int ofc_bench_lloyd_sweep_w(int device, const float *X_dev, const void *w_dev, int w_dtype, int64_t N, int k,
+                            const double *centers, const double *mean, int iters, float *ms_per_launch);
+
 /* one step of k-means++ seeding (sklearn's default init for KMeans(n_clusters=k), the reference's construction at
  * color_kmeans.py:66, KmeanGrids.py:300; algorithm: sklearn/cluster/_kmeans.py:230-262): squared distances of all N
  * samples (centred by `mean`) to the rows X[cand[c]], c < n_cand <= 8, in the expanded form sklearn evaluates,

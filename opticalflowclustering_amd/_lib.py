@@ -83,6 +83,15 @@ _PROTOS = {
     "ofc_lloyd_step_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _i, _vp], _i),
     "ofc_lloyd_inertia_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, C.POINTER(_d)], _i),
     "ofc_lloyd_farthest_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp, _ip], _i),
+    "ofc_kmeans_fit_w": ([_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _i, _d, _vp, _vp, C.POINTER(_d), _ip], _i),
+    "ofc_kmeans_fit_dev_w": ([_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _i, _d, _vp, _vp, _vp, C.POINTER(_d), _ip], _i),
+    "ofc_kmeans_score": ([_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, C.POINTER(_d)], _i),
+    "ofc_lloyd_step_dev_w": ([_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "ofc_lloyd_inertia_dev_w": ([_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, C.POINTER(_d)], _i),
+    "ofc_lloyd_farthest_dev_w": ([_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp, _ip,
+                                  C.POINTER(_d)], _i),
+    "ofc_flow_weights_dev": ([_i, _vp, _i64, _i, _f, _vp], _i),
+    "ofc_bench_lloyd_sweep_w": ([_i, _vp, _vp, _i, _i64, _i, _vp, _vp, _i, C.POINTER(_f)], _i),
     "ofc_kpp_candidates": ([_i, _vp, _i, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "ofc_kpp_seed_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i, _vp, _vp], _i),
     "ofc_kpp_sample_dev": ([_i, _vp, _i64, _vp, _i, _vp], _i),

@@ -30,6 +30,29 @@ def _as_supported(X):
     return np.ascontiguousarray(X)
 
 
+def _as_weights(sample_weight, N):
+    """sklearn's _check_sample_weight for KMeans.fit / score: None stays None, a scalar broadcasts, float32 stays float32
+    and every other dtype becomes float64; a wrong length, a negative or non-finite weight, or a zero sum raise"""
+    if sample_weight is None:
+        return None
+    w = np.asarray(sample_weight)
+    if w.ndim == 0:
+        w = np.full(N, w, dtype=w.dtype)
+    if w.dtype != np.float32:
+        w = w.astype(np.float64)
+    if w.ndim != 1:
+        raise ValueError("Sample weights must be 1D array or scalar")
+    if w.shape != (N,):
+        raise ValueError(f"sample_weight.shape == {w.shape}, expected {(N,)}!")
+    if not np.isfinite(w).all():
+        raise ValueError("Input sample_weight contains NaN or infinity.")
+    if (w < 0).any():
+        raise ValueError("Negative values in data passed to `sample_weight`")
+    if N > 0 and not w.astype(np.float64).sum() > 0:
+        raise ValueError("sum of sample weights must be positive")
+    return np.ascontiguousarray(w)
+
+
 def seeded_rows_init(X, k, random_state=0):
     """k distinct rows (by value, when there are enough distinct rows) picked by a seeded rng"""
     rng = np.random.default_rng(random_state)
@@ -159,14 +182,16 @@ class KMeans:
         return C0
 
     def fit(self, X, y=None, sample_weight=None):
-        if sample_weight is not None:
-            raise ValueError("sample_weight is not supported (the reference never passes it)")
         X = _as_supported(X)
         N, d = X.shape
         k = self.n_clusters
         if N < k:
             raise ValueError(f"n_samples={N} should be >= n_clusters={k}.")
-        C0 = self._init_centers(X)
+        w = _as_weights(sample_weight, N)
+        if w is not None and isinstance(self.init, str) and self.init == "k-means++":
+            raise ValueError("sample_weight together with init='k-means++' is not supported: the seeding on the device "
+                             "draws with unit weights (pass an explicit init or 'seeded-rows')")
+        C0 = self._init_centers(X)          # 'seeded-rows' ignores the weights, as sklearn's array init does
         centers = np.empty((k, d), np.float64)
         labels = np.empty(N, np.int32)
         inertia, n_iter = C.c_double(), C.c_int()
@@ -183,6 +208,10 @@ class KMeans:
             finally:
                 Xd.free()
                 Ld.free()
+        elif w is not None:
+            check(load().ofc_kmeans_fit_w(self.device, ptr(X), _DT[X.dtype], ptr(w), _DT[w.dtype], N, d, k, ptr(C0),
+                                          self.max_iter, self.tol, ptr(centers), ptr(labels), C.byref(inertia),
+                                          C.byref(n_iter)))
         else:
             check(load().ofc_kmeans_fit(self.device, ptr(X), _DT[X.dtype], N, d, k, ptr(C0), self.max_iter,
                                         self.tol, ptr(centers), ptr(labels), C.byref(inertia), C.byref(n_iter)))
@@ -201,13 +230,29 @@ class KMeans:
         check(load().ofc_kmeans_predict(self.device, ptr(X), _DT[X.dtype], N, d, self.n_clusters, ptr(cen), ptr(labels)))
         return labels
 
-    def fit_predict(self, X, y=None):
-        return self.fit(X).labels_
+    def fit_predict(self, X, y=None, sample_weight=None):
+        return self.fit(X, sample_weight=sample_weight).labels_
+
+    def score(self, X, y=None, sample_weight=None):
+        """sklearn's KMeans.score: minus the (weighted) inertia of X against cluster_centers_"""
+        X = _as_supported(X)
+        N, d = X.shape
+        if d != self.cluster_centers_.shape[1]:
+            raise ValueError(f"X has {d} features, but KMeans is expecting {self.cluster_centers_.shape[1]}")
+        w = _as_weights(sample_weight, N)
+        cen = np.ascontiguousarray(self.cluster_centers_, np.float64)
+        inertia = C.c_double()
+        check(load().ofc_kmeans_score(self.device, ptr(X), _DT[X.dtype], ptr(w), _DT[w.dtype] if w is not None else _lib.F32,
+                                      N, d, self.n_clusters, ptr(cen), C.byref(inertia)))
+        return -inertia.value
 
 
-def kmeans_fit_dev(X_ptr, dtype, N, d, init, max_iter=300, tol=1e-4, labels_ptr=None, device=0, colsum=None):
+def kmeans_fit_dev(X_ptr, dtype, N, d, init, max_iter=300, tol=1e-4, labels_ptr=None, device=0, colsum=None,
+                   weights_ptr=None, weight_dtype=_lib.F32):
     """device-resident X (this rank's shard when a communicator is active).  colsum: this rank's column sums when the
     caller already has them (the flow engine emits sum(u), sum(v) with the field): the fit then skips that sweep.
+    weights_ptr: N device-resident sample weights of weight_dtype (F32 or F64; finite, >= 0, not all zero over the ranks),
+    sklearn's fit(X, sample_weight=); None: the unweighted fit.
     -> centers (k,d), inertia, n_iter"""
     C0 = np.ascontiguousarray(init, np.float64)
     k = C0.shape[0]
@@ -216,6 +261,11 @@ def kmeans_fit_dev(X_ptr, dtype, N, d, init, max_iter=300, tol=1e-4, labels_ptr=
     cs = np.ascontiguousarray(colsum, np.float64) if colsum is not None else None
     if cs is not None and cs.shape != (d,):
         raise ValueError(f"colsum must have shape ({d},)")
+    if weights_ptr:
+        check(load().ofc_kmeans_fit_dev_w(device, C.c_void_p(X_ptr), dtype, C.c_void_p(weights_ptr), weight_dtype, N, d, k, ptr(C0),
+                                          max_iter, tol, ptr(cs), ptr(centers), C.c_void_p(labels_ptr) if labels_ptr else None,
+                                          C.byref(inertia), C.byref(n_iter)))
+        return centers, inertia.value, n_iter.value
     check(load().ofc_kmeans_fit_dev_stats(device, C.c_void_p(X_ptr), dtype, N, d, k, ptr(C0), max_iter, tol, ptr(cs), ptr(centers),
                                           C.c_void_p(labels_ptr) if labels_ptr else None, C.byref(inertia), C.byref(n_iter)))
     return centers, inertia.value, n_iter.value

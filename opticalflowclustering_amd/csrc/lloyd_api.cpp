@@ -72,8 +72,12 @@ static LloydScratch &scratch_for(int device)
 
 // empty-cluster relocation (_k_means_common.pyx:167-211) on the all-reduced totals `tot`.
 // Returns with `tot` patched on the device (or untouched when the farthest distance is 0).
+// wdev != nullptr: the fit is weighted.  The farthest sample is still found by its UNWEIGHTED distance; it moves with its
+// weight: sums[old] -= x*w, sums[new] = x*w, wk[new] = w, wk[old] -= w (_k_means_common.pyx:197-211), the product rounded
+// on its own.  Under a communicator the owner's broadcast carries the weight in one more slot.
 static int relocate_empty(LloydScratch &sc, const void *X, int dtype, int64_t N, int d, int k, int kmax,
-                          int nblocks, const uint8_t *labels, const double *mean_h)
+                          int nblocks, const uint8_t *labels, const double *mean_h, const void *wdev = nullptr,
+                          int w_dtype = OFC_F32)
 {
     hipStream_t s = sc.stream;
     const int NV = lloyd_record_len(kmax, d);
@@ -103,7 +107,8 @@ static int relocate_empty(LloydScratch &sc, const void *X, int dtype, int64_t N,
             if (v > best || (v == best && i < bi)) { best = v; bi = i; }
         }
         // global winner across ranks: max distance, ties -> lowest rank (= lowest global index)
-        double rec[LLOYD_DMAX + 3];   // [dist | rank-or-inf | x_c[d] | old label]
+        double rec[LLOYD_DMAX + 3];   // [x_c[d] | old label | weight (weighted fits only)]
+        const int nrec = d + 1 + (wdev ? 1 : 0);
         int owner = 1;
         if (dist_active()) {
             double *dv = sc.far.as<double>();
@@ -129,6 +134,12 @@ static int relocate_empty(LloydScratch &sc, const void *X, int dtype, int64_t N,
             OFC_HIP(hipMemcpyAsync(raw, (const char *)X + (size_t)bi * d * dtype_size(dtype), d * dtype_size(dtype),
                                    hipMemcpyDeviceToHost, s));
             OFC_HIP(hipMemcpyAsync(&lab, labels + bi, 1, hipMemcpyDeviceToHost, s));
+            double wraw = 1.0;
+            float wraw32 = 1.0f;
+            if (wdev && w_dtype == OFC_F32)
+                OFC_HIP(hipMemcpyAsync(&wraw32, (const float *)wdev + bi, sizeof(float), hipMemcpyDeviceToHost, s));
+            else if (wdev)
+                OFC_HIP(hipMemcpyAsync(&wraw, (const double *)wdev + bi, sizeof(double), hipMemcpyDeviceToHost, s));
             OFC_HIP(hipStreamSynchronize(s));
             for (int f = 0; f < d; f++) {
                 double v = dtype == OFC_U8 ? (double)raw[f]
@@ -136,22 +147,25 @@ static int relocate_empty(LloydScratch &sc, const void *X, int dtype, int64_t N,
                 rec[f] = v - mean_h[f];
             }
             rec[d] = (double)lab;
+            if (wdev) rec[d + 1] = w_dtype == OFC_F32 ? (double)wraw32 : wraw;
             excl.push_back(bi);
         }
         if (dist_active()) {
             double *dv = sc.far.as<double>();
-            OFC_HIP(hipMemcpyAsync(dv, rec, sizeof(double) * (d + 1), hipMemcpyHostToDevice, s));
-            OFC_TRY(dist_allreduce_f64(dv, d + 1, DIST_BCAST, s));
-            OFC_HIP(hipMemcpyAsync(rec, dv, sizeof(double) * (d + 1), hipMemcpyDeviceToHost, s));
+            OFC_HIP(hipMemcpyAsync(dv, rec, sizeof(double) * nrec, hipMemcpyHostToDevice, s));
+            OFC_TRY(dist_allreduce_f64(dv, nrec, DIST_BCAST, s));
+            OFC_HIP(hipMemcpyAsync(rec, dv, sizeof(double) * nrec, hipMemcpyDeviceToHost, s));
             OFC_HIP(hipStreamSynchronize(s));
         }
         const int old = (int)rec[d];
+        const double wt = wdev ? rec[d + 1] : 1.0;
         for (int f = 0; f < d; f++) {
-            tot[old * d + f] -= rec[f];
-            tot[j * d + f] = rec[f];
+            const double xw = rec[f] * wt;      // a statement of its own: rounded before it is subtracted (x * 1 is x)
+            tot[old * d + f] -= xw;
+            tot[j * d + f] = xw;
         }
-        w[j] = 1.0;
-        w[old] -= 1.0;
+        w[j] = wt;
+        w[old] -= wt;
     }
     OFC_HIP(hipMemcpyAsync(sc.tot.p, tot.data(), sizeof(double) * NV, hipMemcpyHostToDevice, s));
     OFC_HIP(hipStreamSynchronize(s));
@@ -160,10 +174,12 @@ static int relocate_empty(LloydScratch &sc, const void *X, int dtype, int64_t N,
 
 static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d, int k, const double *init,
                          int max_iter, double tol_rel, double *centers, uint8_t *labels_dev,
-                         double *inertia, int *n_iter, const double *colsum = nullptr)
+                         double *inertia, int *n_iter, const double *colsum = nullptr, const void *wdev = nullptr,
+                         int w_dtype = OFC_F32)
 {
     OFC_REQUIRE(X && init && centers, "null pointer");
     OFC_REQUIRE(dtype >= OFC_U8 && dtype <= OFC_F64, "bad dtype %d", dtype);
+    OFC_REQUIRE(!wdev || w_dtype == OFC_F32 || w_dtype == OFC_F64, "bad weight dtype %d (OFC_F32 or OFC_F64)", w_dtype);
     OFC_REQUIRE(d >= 1 && k >= 1 && max_iter >= 1 && N >= 0, "bad shape");
     if (d > LLOYD_DMAX || k > LLOYD_KMAX) {
         set_error("k=%d, d=%d outside the kernels' range (k <= %d, d <= %d)", k, d, LLOYD_KMAX, LLOYD_DMAX);
@@ -210,7 +226,8 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
     double c0[LLOYD_KMAX * LLOYD_DMAX];
     for (int j = 0; j < k * d; j++) c0[j] = init[j] - mean_h[j % d];
     OFC_HIP(hipMemcpyAsync(st->centers, c0, sizeof(double) * k * d, hipMemcpyHostToDevice, s));
-    const int prune = prune_policy_for(dtype, N, d, k);
+    // a weighted fit runs the plain sweeps: the tile metadata (cached per-tile sums) is unweighted
+    const int prune = wdev ? LLOYD_PRUNE_OFF : prune_policy_for(dtype, N, d, k);
     if (prune) {
         const size_t need = (size_t)(N >> 6) * 16;
         if (sc.tile_box.bytes < need) {
@@ -262,6 +279,9 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
                 OFC_TRY(launch_lloyd_tiles((const float *)X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, nullptr,
                                            sc.partial.as<double>(), nblocks, LLOYD_WHAT_SWEEP,
                                            tiles == 1 ? sc.tile_meta.as<double>() : nullptr, s));
+            else if (wdev)
+                OFC_TRY(launch_lloyd_assign_w(X, dtype, wdev, w_dtype, N, d, k, st, labels_dev, sc.partial.as<double>(),
+                                              nblocks, labelled ? 1 : 3, it + w == 0, s));
             else
                 OFC_TRY(launch_lloyd_assign(X, dtype, N, d, k, st, labels_dev, sc.partial.as<double>(), nblocks,
                                             labelled ? 1 : 3, it + w == 0, s));
@@ -291,13 +311,20 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
                     sc.prune_stats[4] += 1;
                 }
             }
+            if (wdev && it + w == 0) {
+                // sklearn refuses weights whose sum is not positive (_check_sample_weight); here every cluster would be
+                // empty and relocated in each of max_iter iterations.  The counts are all-reduced: every rank returns.
+                double wsum = 0;
+                for (int j = 0; j < k; j++) wsum += S.counts[j];
+                if (!(wsum > 0)) { set_error("sum of sample weights must be positive"); return OFC_EINVAL; }
+            }
             if (S.n_empty > 0) {              // the device stalled here; iterations w+1.. of the window were no-ops
                 const bool was_labelled = labelled;
                 if (!labelled) {   // materialise this iteration's labels (st->centers is still the E-step's input)
                     OFC_TRY(launch_lloyd_assign(X, dtype, N, d, k, st, labels_dev, nullptr, nblocks, 0, 0, s));
                     labelled = true;
                 }
-                OFC_TRY(relocate_empty(sc, X, dtype, N, d, k, kmax, nblocks, labels_dev, mean_h));
+                OFC_TRY(relocate_empty(sc, X, dtype, N, d, k, kmax, nblocks, labels_dev, mean_h, wdev, w_dtype));
                 S.valid = 0;
                 OFC_TRY(launch_lloyd_update(st, tot, k, d, 1, was_labelled, it + w == 0, Ng, tol_rel, sc.status_dev + w, s));
                 OFC_HIP(hipStreamSynchronize(s));
@@ -316,8 +343,12 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
     if (final_tiles)                        // the fit's tile metadata is valid and most tiles pass: those are not read
         OFC_TRY(launch_lloyd_tiles((const float *)X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, labels_dev,
                                    sc.partial.as<double>(), nblocks, LLOYD_WHAT_FINAL, nullptr, s));
+    else if (!strict && wdev)
+        OFC_TRY(launch_lloyd_assign_w(X, dtype, wdev, w_dtype, N, d, k, st, labels_dev, sc.partial.as<double>(), nblocks, 2, 0, s));
     else if (!strict)
         OFC_TRY(launch_lloyd_assign(X, dtype, N, d, k, st, labels_dev, sc.partial.as<double>(), nblocks, 2, 0, s));
+    else if (wdev)
+        OFC_TRY(launch_lloyd_inertia_w(X, dtype, wdev, w_dtype, N, d, st, labels_dev, sc.partial.as<double>(), nblocks, s));
     else
         OFC_TRY(launch_lloyd_inertia(X, dtype, N, d, st, labels_dev, sc.partial.as<double>(), nblocks, s));
     OFC_TRY(launch_reduce_records(sc.partial.as<double>(), nblocks, 1, tot, s));
@@ -881,6 +912,215 @@ int ofc_kpp_sample_dev(int device, const double *w_dev, int64_t N, const double 
     OFC_TRY(launch_kpp_sample(nullptr, OFC_F64, N, 1, nullptr, nullptr, KPP_PREV_NONE, w_dev, cs.as<double>(), ss.as<double>(),
                               r, n, 0.0, out.as<int64_t>(), nullptr, nullptr));
     OFC_HIP(hipMemcpy(idx, out.p, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+/* ---- sample weights, see include/ofc.h ---- */
+namespace {
+int check_w_dtype(int w_dtype)
+{
+    if (w_dtype != OFC_F32 && w_dtype != OFC_F64) {
+        set_error("bad weight dtype %d (OFC_F32 or OFC_F64)", w_dtype);
+        return OFC_EINVAL;
+    }
+    return OFC_OK;
+}
+
+// host weights: finite, non-negative, positive sum (sklearn's _check_sample_weight + the zero-sum refusal)
+int check_host_weights(const void *w, int w_dtype, int64_t N)
+{
+    double sum = 0;
+    for (int64_t i = 0; i < N; i++) {
+        const double v = w_dtype == OFC_F32 ? (double)((const float *)w)[i] : ((const double *)w)[i];
+        if (!std::isfinite(v)) { set_error("sample_weight[%lld] is not finite", (long long)i); return OFC_EINVAL; }
+        if (v < 0) { set_error("sample_weight[%lld] is negative", (long long)i); return OFC_EINVAL; }
+        sum += v;
+    }
+    if (!(sum > 0)) { set_error("sum of sample weights must be positive"); return OFC_EINVAL; }
+    return OFC_OK;
+}
+}  // namespace
+
+int ofc_kmeans_fit_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d, int k,
+                         const double *init, int max_iter, double tol_rel, const double *colsum, double *centers,
+                         uint8_t *labels_dev, double *inertia, int *n_iter)
+{
+    if (w_dev) OFC_TRY(check_w_dtype(w_dtype));
+    return lloyd_fit_dev(device, X_dev, dtype, N, d, k, init, max_iter, tol_rel, centers, labels_dev, inertia, n_iter, colsum,
+                         w_dev, w_dtype);
+}
+
+int ofc_kmeans_fit_w(int device, const void *X, int dtype, const void *w, int w_dtype, int64_t N, int d, int k,
+                     const double *init, int max_iter, double tol_rel, double *centers, int32_t *labels, double *inertia,
+                     int *n_iter)
+{
+    OFC_REQUIRE(X && w && init && centers, "null pointer");
+    OFC_REQUIRE(dtype >= OFC_U8 && dtype <= OFC_F64 && d >= 1 && N >= 0, "bad arguments");
+    OFC_TRY(check_w_dtype(w_dtype));
+    OFC_REQUIRE(N >= k, "n_samples=%lld should be >= n_clusters=%d.", (long long)N, k);
+    OFC_TRY(check_host_weights(w, w_dtype, N));
+    OFC_TRY(ensure_device(device));
+    DevBuf dX, dW, dL;
+    const size_t bytes = (size_t)N * d * dtype_size(dtype), wbytes = (size_t)N * dtype_size(w_dtype);
+    OFC_TRY(dX.alloc(std::max<size_t>(bytes, 16)));
+    OFC_TRY(dW.alloc(std::max<size_t>(wbytes, 16)));
+    OFC_TRY(dL.alloc((size_t)std::max<int64_t>(N, 1)));
+    OFC_HIP(hipMemcpy(dX.p, X, bytes, hipMemcpyHostToDevice));
+    OFC_HIP(hipMemcpy(dW.p, w, wbytes, hipMemcpyHostToDevice));
+    OFC_TRY(lloyd_fit_dev(device, dX.p, dtype, N, d, k, init, max_iter, tol_rel, centers, dL.as<uint8_t>(), inertia, n_iter,
+                          nullptr, dW.p, w_dtype));
+    if (labels) {
+        std::vector<uint8_t> l8((size_t)N);
+        OFC_HIP(hipMemcpy(l8.data(), dL.p, (size_t)N, hipMemcpyDeviceToHost));
+        widen_labels(l8.data(), N, labels);
+    }
+    return OFC_OK;
+}
+
+int ofc_kmeans_score(int device, const void *X, int dtype, const void *w, int w_dtype, int64_t N, int d, int k,
+                     const double *centers, double *inertia)
+{
+    OFC_REQUIRE(X && centers && inertia, "null pointer");
+    OFC_REQUIRE(dtype >= OFC_U8 && dtype <= OFC_F64 && N >= 0, "bad arguments");
+    OFC_TRY(check_kd(k, d));
+    if (w) {
+        OFC_TRY(check_w_dtype(w_dtype));
+        OFC_TRY(check_host_weights(w, w_dtype, N));
+    }
+    OFC_TRY(ensure_device(device));
+    DevBuf dX, dW, dL;
+    const size_t bytes = (size_t)N * d * dtype_size(dtype), wbytes = w ? (size_t)N * dtype_size(w_dtype) : 0;
+    OFC_TRY(dX.alloc(std::max<size_t>(bytes, 16)));
+    OFC_TRY(dL.alloc((size_t)std::max<int64_t>(N, 1)));
+    OFC_HIP(hipMemcpy(dX.p, X, bytes, hipMemcpyHostToDevice));
+    if (w) {
+        OFC_TRY(dW.alloc(std::max<size_t>(wbytes, 16)));
+        OFC_HIP(hipMemcpy(dW.p, w, wbytes, hipMemcpyHostToDevice));
+    }
+    // the centres as given (KMeans.score does not centre X): mean 0
+    StepCtx c;
+    OFC_TRY(c.init(N, 2));
+    double zero[LLOYD_DMAX] = {0, 0, 0, 0};
+    OFC_TRY(c.set(zero, centers, k, d));
+    LloydState *st = c.state.as<LloydState>();
+    if (w)
+        OFC_TRY(launch_lloyd_assign_w(dX.p, dtype, dW.p, w_dtype, N, d, k, st, dL.as<uint8_t>(), c.partial.as<double>(),
+                                      c.nblocks, 2, 0, nullptr));
+    else
+        OFC_TRY(launch_lloyd_assign(dX.p, dtype, N, d, k, st, dL.as<uint8_t>(), c.partial.as<double>(), c.nblocks, 2, 0, nullptr));
+    OFC_TRY(launch_reduce_records(c.partial.as<double>(), c.nblocks, 1, c.tot.as<double>(), nullptr));
+    OFC_HIP(hipMemcpy(inertia, c.tot.p, sizeof(double), hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+int ofc_lloyd_step_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d, int k,
+                         const double *mean, const double *centers_c, uint8_t *labels_dev, double *record)
+{
+    OFC_REQUIRE(X_dev && w_dev && mean && centers_c && labels_dev && record && N >= 0, "bad arguments");
+    OFC_TRY(check_w_dtype(w_dtype));
+    OFC_TRY(check_kd(k, d));
+    OFC_TRY(ensure_device(device));
+    const int kmax = lloyd_kmax(k), NV = lloyd_record_len(kmax, d);
+    StepCtx c;
+    OFC_TRY(c.init(N, NV));
+    OFC_TRY(c.set(mean, centers_c, k, d));
+    LloydState *st = c.state.as<LloydState>();
+    OFC_TRY(launch_lloyd_assign_w(X_dev, dtype, w_dev, w_dtype, N, d, k, st, labels_dev, c.partial.as<double>(), c.nblocks, 1, 0, nullptr));
+    OFC_TRY(launch_reduce_records(c.partial.as<double>(), c.nblocks, NV, c.tot.as<double>(), nullptr));
+    std::vector<double> t(NV);
+    OFC_HIP(hipMemcpy(t.data(), c.tot.p, sizeof(double) * NV, hipMemcpyDeviceToHost));
+    for (int j = 0; j < k; j++) {
+        for (int f = 0; f < d; f++) record[j * d + f] = t[j * d + f];
+        record[k * d + j] = t[kmax * d + j];
+    }
+    record[k * d + k] = t[kmax * d + kmax];
+    return OFC_OK;
+}
+
+int ofc_lloyd_inertia_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d, int k,
+                            const double *mean, const double *centers_c, const uint8_t *labels_dev, double *inertia)
+{
+    OFC_REQUIRE(X_dev && w_dev && mean && centers_c && labels_dev && inertia && N >= 0, "bad arguments");
+    OFC_TRY(check_w_dtype(w_dtype));
+    OFC_TRY(check_kd(k, d));
+    OFC_TRY(ensure_device(device));
+    StepCtx c;
+    OFC_TRY(c.init(N, 2));
+    OFC_TRY(c.set(mean, centers_c, k, d));
+    OFC_TRY(launch_lloyd_inertia_w(X_dev, dtype, w_dev, w_dtype, N, d, c.state.as<LloydState>(), labels_dev,
+                                   c.partial.as<double>(), c.nblocks, nullptr));
+    OFC_TRY(launch_reduce_records(c.partial.as<double>(), c.nblocks, 1, c.tot.as<double>(), nullptr));
+    OFC_HIP(hipMemcpy(inertia, c.tot.p, sizeof(double), hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+int ofc_lloyd_farthest_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d, int k,
+                             const double *mean, const double *centers_c, const uint8_t *labels_dev, const int64_t *excl,
+                             int n_excl, double *dist2, int64_t *index, double *x_c, int *label, double *weight)
+{
+    OFC_REQUIRE(w_dev && weight, "bad arguments");
+    OFC_TRY(check_w_dtype(w_dtype));
+    OFC_TRY(ofc_lloyd_farthest_dev(device, X_dev, dtype, N, d, k, mean, centers_c, labels_dev, excl, n_excl, dist2, index,
+                                   x_c, label));
+    *weight = 0.0;
+    if (*index >= 0) {
+        if (w_dtype == OFC_F32) {
+            float v;
+            OFC_HIP(hipMemcpy(&v, (const float *)w_dev + *index, sizeof(float), hipMemcpyDeviceToHost));
+            *weight = (double)v;
+        } else {
+            OFC_HIP(hipMemcpy(weight, (const double *)w_dev + *index, sizeof(double), hipMemcpyDeviceToHost));
+        }
+    }
+    return OFC_OK;
+}
+
+int ofc_flow_weights_dev(int device, const float *flow_dev, int64_t n, int kind, float thr, float *w_dev)
+{
+    OFC_REQUIRE(flow_dev && w_dev && n >= 0, "bad arguments");
+    OFC_REQUIRE(kind == 0 || kind == 1, "kind = %d (0 magnitude, 1 moving)", kind);
+    OFC_REQUIRE(kind == 0 || (std::isfinite(thr) && thr >= 0), "thr must be finite and >= 0");
+    OFC_TRY(ensure_device(device));
+    OFC_TRY(launch_flow_weights(flow_dev, n, kind, thr, w_dev, nullptr));
+    OFC_HIP(hipStreamSynchronize(nullptr));
+    return OFC_OK;
+}
+
+int ofc_bench_lloyd_sweep_w(int device, const float *X_dev, const void *w_dev, int w_dtype, int64_t N, int k,
+                            const double *centers, const double *mean, int iters, float *ms_per_launch)
+{
+    OFC_REQUIRE(X_dev && w_dev && centers && mean && ms_per_launch && iters >= 1 && N >= 64, "bad arguments");
+    OFC_TRY(check_w_dtype(w_dtype));
+    OFC_TRY(check_kd(k, 2));
+    OFC_TRY(ensure_device(device));
+    LloydScratch &sc = scratch_for(device);
+    std::lock_guard<std::mutex> lock(sc.mu);
+    OFC_TRY(sc.init());
+    hipStream_t s = sc.stream;
+    const int nblocks = lloyd_grid(N);
+    LloydState *st = sc.state.as<LloydState>();
+    OFC_HIP(hipMemsetAsync(st, 0, sizeof(LloydState), s));
+    double c0[LLOYD_KMAX * LLOYD_DMAX];
+    for (int j = 0; j < k * 2; j++) c0[j] = centers[j] - mean[j % 2];
+    OFC_HIP(hipMemcpyAsync(st->mean, mean, sizeof(double) * 2, hipMemcpyHostToDevice, s));
+    OFC_HIP(hipMemcpyAsync(st->centers, c0, sizeof(double) * k * 2, hipMemcpyHostToDevice, s));
+    OFC_TRY(launch_lloyd_set_centers(st, k, 2, s));
+    auto launch = [&]() -> int {
+        return launch_lloyd_assign_w(X_dev, OFC_F32, w_dev, w_dtype, N, 2, k, st, nullptr, sc.partial.as<double>(), nblocks, 3, 0, s);
+    };
+    hipEvent_t e0, e1;
+    OFC_HIP(hipEventCreate(&e0));
+    OFC_HIP(hipEventCreate(&e1));
+    for (int w = 0; w < 2; w++) OFC_TRY(launch());
+    OFC_HIP(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; i++) OFC_TRY(launch());
+    OFC_HIP(hipEventRecord(e1, s));
+    OFC_HIP(hipEventSynchronize(e1));
+    float ms = 0;
+    OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
+    *ms_per_launch = ms / iters;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
     return OFC_OK;
 }
 

@@ -82,6 +82,16 @@ int launch_lloyd_farthest(const void *X, int dtype, int64_t N, int d, const Lloy
                           const double *c_old, const uint8_t *labels, const int64_t *excl, int n_excl,
                           double *out, int nblocks, hipStream_t s);
 
+// the sweeps with sample weights (lloyd_weighted.hip): W is N weights of w_dtype (OFC_F32 / OFC_F64, 16-byte aligned).
+// mode 1 / 2 / 3 and the record as launch_lloyd_assign's, with the weight sums in the count slots and the inertia weighted
+int launch_lloyd_assign_w(const void *X, int dtype, const void *W, int w_dtype, int64_t N, int d, int k,
+                          const LloydState *st, uint8_t *labels, double *partial, int nblocks, int mode, int first,
+                          hipStream_t s);
+int launch_lloyd_inertia_w(const void *X, int dtype, const void *W, int w_dtype, int64_t N, int d, const LloydState *st,
+                           const uint8_t *labels, double *partial, int nblocks, hipStream_t s);
+// w[i] = |flow[i]| (kind 0) or flow[i] . flow[i] >= thr^2 ? 1 : 0 (kind 1) over n (u,v) vectors, f32
+int launch_flow_weights(const float *flow, int64_t n, int kind, float thr, float *w, hipStream_t s);
+
 // k-means++ seeding step; partial: [nblocks][8] potentials per candidate
 int launch_kpp_candidates(const void *X, int dtype, int64_t N, int d, const double *mean, const double *cand_centred,
                           int n_cand, const double *closest, double *out, double *partial, int nblocks, hipStream_t s);

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, stages
 from ._lib import DeviceBuffer, FbParams, check, load
 from .cluster import kmeans_fit_dev, kmeans_plusplus_dev
 from .flow import FlowEngine
@@ -54,6 +54,7 @@ class ClipPipeline:
         self.n_batches = len(self.schedule)
         self.uv_sums = DeviceBuffer(self.n_batches * 16, device)
         self._sums_valid = False
+        self.weights = None                 # N f32 sample weights for run_kmeans, allocated on first use
 
     def synth(self, t0=0, seed=0):
         """fill the resident clip with synthetic frames t0 .. t0+n_frames-1"""
@@ -81,13 +82,39 @@ class ClipPipeline:
         for e in self.engines:
             e.sync()
 
-    def run_kmeans(self, init, max_iter=300, tol=1e-4, k=None, random_state=None, n_global=None):
+    def _weights_ptr(self, sample_weight, N):
+        if sample_weight is None:
+            return None
+        if self.weights is None:
+            self.weights = DeviceBuffer(N * 4, self.device)
+        if isinstance(sample_weight, str) or isinstance(sample_weight, tuple):
+            kind, thr = (sample_weight, 0.0) if isinstance(sample_weight, str) else sample_weight
+            if kind not in ("magnitude", "moving") or (kind == "moving") != isinstance(sample_weight, tuple):
+                raise ValueError("sample_weight should be None, 'magnitude', ('moving', thr) or an array, "
+                                 f"got {sample_weight!r}")
+            stages.flow_weights_dev(self.flows.ptr, N, kind, thr, self.weights.ptr, self.device)
+        else:
+            w = np.ascontiguousarray(sample_weight, np.float32).ravel()
+            if w.shape != (N,):
+                raise ValueError(f"sample_weight has {w.size} entries, expected {N}")
+            if not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError("sample_weight must be finite and >= 0")
+            self.weights.upload(w)
+        return self.weights.ptr
+
+    def run_kmeans(self, init, max_iter=300, tol=1e-4, k=None, random_state=None, n_global=None, sample_weight=None):
         """Lloyd over all local (u,v) vectors (global when a communicator is active).
         init: (k,2) array, or 'k-means++' with k= and random_state=: sklearn's seeding on the resident vectors
         (cluster.kmeans_plusplus_dev).  Under a communicator every rank passes the same random_state, and n_global = the
-        number of (u,v) vectors over all ranks.  -> centers (k,2), inertia, n_iter"""
+        number of (u,v) vectors over all ranks.
+        sample_weight: None, 'magnitude' (a vector counts by its length), ('moving', thr) (1 where the length reaches thr,
+        else 0), or one value per local vector (kept as f32).  The weights live in a device buffer allocated on first use;
+        not available together with init='k-means++'.  -> centers (k,2), inertia, n_iter"""
         self.sync()
         N = self.n_pairs * self.W * self.H
+        if sample_weight is not None and isinstance(init, str):
+            raise ValueError("sample_weight together with init='k-means++' is not supported (the seeding draws with unit weights)")
+        wptr = self._weights_ptr(sample_weight, N)
         colsum = None
         if self._sums_valid:
             per_batch = self.uv_sums.download((self.n_batches, 2), np.float64)
@@ -99,7 +126,8 @@ class ClipPipeline:
                 raise ValueError(f"init should be a (k,2) array or 'k-means++' together with k=, got {init!r}, k={k!r}")
             init, _ = kmeans_plusplus_dev(self.flows.ptr, _lib.F32, N, 2, int(k), random_state, device=self.device,
                                           colsum=colsum, n_global=n_global)
-        return kmeans_fit_dev(self.flows.ptr, _lib.F32, N, 2, init, max_iter, tol, self.labels.ptr, self.device, colsum=colsum)
+        return kmeans_fit_dev(self.flows.ptr, _lib.F32, N, 2, init, max_iter, tol, self.labels.ptr, self.device, colsum=colsum,
+                              weights_ptr=wptr, weight_dtype=_lib.F32)
 
     def sample_uv(self, idx):
         """host copy of a few (u,v) rows (for choosing the initial centres)"""
@@ -117,5 +145,6 @@ class ClipPipeline:
     def close(self):
         for e in self.engines:
             e.close()
-        for b in (self.frames, self.flows, self.labels, self.uv_sums):
-            b.free()
+        for b in (self.frames, self.flows, self.labels, self.uv_sums, self.weights):
+            if b is not None:
+                b.free()

@@ -3,6 +3,8 @@ sklearn's _kmeans_single_lloyd, _kmeans.py:624-752), but with the per-iteration 
 caller-supplied collective, so that shards can be combined by ANY transport -- torch.distributed with
 gloo across nodes, or RCCL.  Every rank holds a contiguous shard of the rows (frame-sharded (u,v) vectors)
 and all k centres; per iteration ONE all-reduce (sum) of [k*d sums | k counts | n_changed].
+With sample weights (sklearn's fit(X, sample_weight=)) the sums are of x*w, the counts are weight sums, and a relocated
+sample moves with its weight; a backend without weights returns counts and four values from farthest(), as before.
 
 `backend` supplies the four shard-local passes; DeviceShard runs them on the MI355X through the C ABI.
 (The CPU tests drive the identical function with an oracle-backed shard and a gloo all-reduce.)"""
@@ -35,10 +37,12 @@ def _np_sum_small(a):
 
 
 class DeviceShard:
-    """a device-resident shard X_dev (N x d of dtype) + its u8 label buffer"""
+    """a device-resident shard X_dev (N x d of dtype) + its u8 label buffer; weights_ptr: N device-resident sample
+    weights of weight_dtype (F32 or F64; finite and >= 0), None for the unweighted fit"""
 
-    def __init__(self, X_ptr, dtype, N, d, labels_ptr=None, device=0):
+    def __init__(self, X_ptr, dtype, N, d, labels_ptr=None, device=0, weights_ptr=None, weight_dtype=_lib.F32):
         self.X, self.dtype, self.N, self.d, self.device = X_ptr, dtype, int(N), int(d), device
+        self.W, self.wdtype = weights_ptr, weight_dtype
         self._own = None
         if labels_ptr is None:
             self._own = _lib.DeviceBuffer(max(self.N, 1), device)
@@ -55,6 +59,11 @@ class DeviceShard:
     def step(self, mean, centers_c, accumulate=True):
         k = len(centers_c)
         rec = np.zeros(k * self.d + k + 1, np.float64)
+        if self.W and accumulate:
+            check(load().ofc_lloyd_step_dev_w(self.device, C.c_void_p(self.X), self.dtype, C.c_void_p(self.W), self.wdtype,
+                                              self.N, self.d, k, ptr(np.ascontiguousarray(mean, np.float64)),
+                                              ptr(np.ascontiguousarray(centers_c, np.float64)), C.c_void_p(self.labels), ptr(rec)))
+            return rec
         check(load().ofc_lloyd_step_dev(self.device, C.c_void_p(self.X), self.dtype, self.N, self.d, k,
                                         ptr(np.ascontiguousarray(mean, np.float64)), ptr(np.ascontiguousarray(centers_c, np.float64)),
                                         C.c_void_p(self.labels), 1 if accumulate else 0, ptr(rec)))
@@ -62,6 +71,12 @@ class DeviceShard:
 
     def inertia(self, mean, centers_c):
         v = C.c_double()
+        if self.W:
+            check(load().ofc_lloyd_inertia_dev_w(self.device, C.c_void_p(self.X), self.dtype, C.c_void_p(self.W), self.wdtype,
+                                                 self.N, self.d, len(centers_c), ptr(np.ascontiguousarray(mean, np.float64)),
+                                                 ptr(np.ascontiguousarray(centers_c, np.float64)), C.c_void_p(self.labels),
+                                                 C.byref(v)))
+            return v.value
         check(load().ofc_lloyd_inertia_dev(self.device, C.c_void_p(self.X), self.dtype, self.N, self.d, len(centers_c),
                                            ptr(np.ascontiguousarray(mean, np.float64)), ptr(np.ascontiguousarray(centers_c, np.float64)),
                                            C.c_void_p(self.labels), C.byref(v)))
@@ -71,6 +86,14 @@ class DeviceShard:
         ex = np.ascontiguousarray(excl, np.int64) if len(excl) else None
         d2, idx, lab = C.c_double(), C.c_int64(), C.c_int()
         xc = np.zeros(self.d, np.float64)
+        if self.W:                                   # a fifth value: the winner's weight
+            wt = C.c_double()
+            check(load().ofc_lloyd_farthest_dev_w(self.device, C.c_void_p(self.X), self.dtype, C.c_void_p(self.W), self.wdtype,
+                                                  self.N, self.d, len(centers_c), ptr(np.ascontiguousarray(mean, np.float64)),
+                                                  ptr(np.ascontiguousarray(centers_c, np.float64)), C.c_void_p(self.labels),
+                                                  ptr(ex), len(excl), C.byref(d2), C.byref(idx), ptr(xc), C.byref(lab),
+                                                  C.byref(wt)))
+            return d2.value, idx.value, xc, lab.value, wt.value
         check(load().ofc_lloyd_farthest_dev(self.device, C.c_void_p(self.X), self.dtype, self.N, self.d, len(centers_c),
                                             ptr(np.ascontiguousarray(mean, np.float64)), ptr(np.ascontiguousarray(centers_c, np.float64)),
                                             C.c_void_p(self.labels), ptr(ex), len(excl), C.byref(d2), C.byref(idx), ptr(xc), C.byref(lab)))
@@ -79,7 +102,9 @@ class DeviceShard:
 
 def fit_sharded(shard, init, max_iter=300, tol=1e-4, allreduce=None, rank=0):
     """-> (cluster_centers_ (k,d), inertia_, n_iter_); labels stay in the shard.
-    allreduce(np.float64 array, op) with op in {'sum','max','min'} returns the reduced array."""
+    allreduce(np.float64 array, op) with op in {'sum','max','min'} returns the reduced array.
+    A weighted shard's step() returns weight sums in the count slots and its farthest() a fifth value, the winner's sample
+    weight (absent: 1.0); relocation then follows _k_means_common.pyx:197-211."""
     if allreduce is None:
         allreduce = lambda a, op: a                                        # noqa: E731  (single shard)
     init = np.ascontiguousarray(init, np.float64)
@@ -96,28 +121,31 @@ def fit_sharded(shard, init, max_iter=300, tol=1e-4, allreduce=None, rank=0):
     for it in range(max_iter):
         rec = allreduce(shard.step(mean, c, True), "sum")
         sums, w, n_changed = rec[:k * d].reshape(k, d).copy(), rec[k * d:k * d + k].copy(), rec[k * d + k]
+        if it == 0 and not w.sum() > 0:
+            raise ValueError("sum of sample weights must be positive")
         if (w == 0).any():                                                 # _relocate_empty_clusters_dense
             excl, first = [], True
             for j in range(k):
                 if w[j] != 0:
                     continue
-                d2, idx, xc, lab = shard.farthest(mean, c, excl)
+                d2, idx, xc, lab, *rest = shard.farthest(mean, c, excl)
                 g = allreduce(np.array([d2]), "max")[0]
                 cand = float(rank) if (idx >= 0 and d2 == g) else 1e300
                 owner = allreduce(np.array([cand]), "min")[0] == float(rank) and idx >= 0 and d2 == g
                 if first and not g > 0:
                     break
                 first = False
-                msg = np.zeros(d + 1)
+                msg = np.zeros(d + 2)
                 if owner:
-                    msg[:d], msg[d] = xc, float(lab)
+                    msg[:d], msg[d], msg[d + 1] = xc, float(lab), float(rest[0]) if rest else 1.0
                     excl.append(idx)
                 msg = allreduce(msg, "sum")
-                old = int(msg[d])
-                sums[old] -= msg[:d]
-                sums[j] = msg[:d]
-                w[j] = 1.0
-                w[old] -= 1.0
+                old, wt = int(msg[d]), msg[d + 1]
+                xw = msg[:d] * wt
+                sums[old] -= xw
+                sums[j] = xw
+                w[j] = wt
+                w[old] -= wt
         amax = int(np.argmax(w))                                           # _average_centers (in-place quirk kept)
         cnew = sums.copy()
         for j in range(k):

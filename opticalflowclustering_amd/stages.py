@@ -89,3 +89,23 @@ def bench_lloyd_sweep(X_ptr, N, centers, mean, what, iters=10, device=0):
     ms = C.c_float()
     check(load().ofc_bench_lloyd_sweep(device, C.c_void_p(X_ptr), N, len(cen), ptr(cen), ptr(mean), what, iters, C.byref(ms)))
     return ms.value
+
+
+def bench_lloyd_sweep_w(X_ptr, w_ptr, w_dtype, N, centers, mean, iters=10, device=0):
+    """ms per launch of the label-less weighted Lloyd sweep over a resident (u,v) stream and its weights
+    (ofc_bench_lloyd_sweep_w): bench_lloyd_sweep(what=0) plus the weight stream"""
+    cen = np.ascontiguousarray(centers, np.float64)
+    mean = np.ascontiguousarray(mean, np.float64)
+    ms = C.c_float()
+    check(load().ofc_bench_lloyd_sweep_w(device, C.c_void_p(X_ptr), C.c_void_p(w_ptr), w_dtype, N, len(cen), ptr(cen), ptr(mean),
+                                         iters, C.byref(ms)))
+    return ms.value
+
+
+def flow_weights_dev(flow_ptr, n, kind, thr, w_ptr, device=0):
+    """sample weights from a resident (u,v) field (ofc_flow_weights_dev): kind 'magnitude' -> |(u,v)|, 'moving' -> 1 where
+    |(u,v)| >= thr, else 0; n f32 weights written to w_ptr"""
+    kinds = {"magnitude": 0, "moving": 1}
+    if kind not in kinds:
+        raise ValueError(f"weight kind should be 'magnitude' or 'moving', got {kind!r}")
+    check(load().ofc_flow_weights_dev(device, C.c_void_p(flow_ptr), n, kinds[kind], float(thr), C.c_void_p(w_ptr)))
