@@ -329,6 +329,28 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
 /* the sampling stage on its own (single rank; test and inspection hook):
  * idx[j] = min(searchsorted(cumsum(w_dev[0..N)), r[j], side='left'), N-1), j < n <= 8, 1 <= N <= 2^30; w_dev: N f64 >= 0 */
 int ofc_kpp_sample_dev(int device, const double *w_dev, int64_t N, const double *r, int n, int64_t *idx);
+/* ofc_kpp_seed_dev with sample weights: sklearn's _kmeans_plusplus(..., sample_weight) (_kmeans.py:174-272).  The data
+ * is centred by the UNWEIGHTED column mean, as KMeans.fit does.  w_dev: this rank's N weights of w_dtype (OFC_F32 or
+ * OFC_F64, 16-byte aligned; finite, >= 0, positive sum over all ranks), widened to f64.  They decide
+ *   the first centre: the one number RandomState.choice(N, p=w/w.sum()) consumes is u_first in [0,1); the centre is the
+ *           smallest GLOBAL row i with cumsum(w)[i] > u_first * W (W: the global weight sum, formed in the same fixed
+ *           order), the last row of positive weight when rounding leaves none.  Never a row of weight zero.
+ *   every later draw: rand_vals = u[c-1][:] * current_pot are looked up (side='left', clipped to N-1) in
+ *           cumsum(w * closest), each product rounded on its own before it is added
+ *   every candidate's potential: sum_i w[i] * min(closest[i], d(x_i, cand)).  The first minimum wins.
+ * closest[] itself stays unweighted.  Everything else -- u, colsum, centers, indices, ranges, the result being the same
+ * on every rank, a rank with an empty shard or only zero weights -- is ofc_kpp_seed_dev's.
+ * OFC_EINVAL in addition: w_dev NULL or misaligned, a bad w_dtype, u_first outside [0,1) (all before anything is
+ * launched), and a global weight sum that is not positive ("sum of sample weights must be positive"). */
+int ofc_kpp_seed_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d, int k,
+                       const double *colsum, double u_first, const double *u, int n_trials, double *centers,
+                       int64_t *indices);
+/* the weighted sampling stage on its own (single rank; test and inspection hook):
+ * idx[j] = min(searchsorted(cumsum(w[0..N) * v[0..N)), r[j], side), N-1), j < n <= 8, 1 <= N <= 2^30, each product
+ * rounded on its own.  w_dev: N f32 or f64 (w_dtype), 16-byte aligned; v_dev: N f64 >= 0, or NULL for ones;
+ * side: 0 = 'left', 1 = 'right'.  total[0] = the sum of all N values as the device formed it. */
+int ofc_kpp_sample_dev_w(int device, const void *w_dev, int w_dtype, const double *v_dev, int64_t N, const double *r, int n,
+                         int side, int64_t *idx, double *total);
 #define OFC_KPP_CHUNK 1024   /* samples per partial sum of the two-level cumulative sum */
 /* many small independent problems in one launch (the per-grid-cell shape of KmeanGrids.py:376-392):
  * problem p owns rows [offsets[p], offsets[p+1]) of X (u8, d = 4); init/centers: P x k x d f64;

@@ -95,6 +95,8 @@ _PROTOS = {
     "ofc_kpp_candidates": ([_i, _vp, _i, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "ofc_kpp_seed_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i, _vp, _vp], _i),
     "ofc_kpp_sample_dev": ([_i, _vp, _i64, _vp, _i, _vp], _i),
+    "ofc_kpp_seed_dev_w": ([_i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _d, _vp, _i, _vp, _vp], _i),
+    "ofc_kpp_sample_dev_w": ([_i, _vp, _i, _vp, _i64, _vp, _i, _i, _vp, _vp], _i),
     "ofc_kmeans_fit_batched": ([_i, _vp, _vp, _i, _i, _i, _vp, _i, _d, _vp, _vp, _vp, _vp], _i),
     "ofc_grid_kmeans": ([_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp], _i),
     "ofc_grid_kmeans_dev": ([_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _i, _vp, _vp], _i),

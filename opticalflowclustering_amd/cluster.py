@@ -74,9 +74,12 @@ def check_random_state(seed):
     raise ValueError(f"{seed!r} cannot be used to seed a numpy.random.RandomState instance")
 
 
-def kmeans_plusplus(X, n_clusters, random_state=None, n_local_trials=None, device=0, _step=None):
+def kmeans_plusplus(X, n_clusters, random_state=None, n_local_trials=None, device=0, _step=None, sample_weight=None):
     """sklearn's _kmeans_plusplus (_kmeans.py:174-272) as KMeans.fit runs it: on the column-centred data, unit sample
-    weights.  The O(N d trials) part of every step -- distances of all samples to the candidate rows, the minimum
+    weights unless sample_weight is given (then, as KMeans.fit(X, sample_weight=) seeds: the weights decide the first
+    centre, the distribution of every later draw and every candidate's potential; KMeans(init=C0).fit(X,
+    sample_weight=w) from the returned centres is the two-step form of sklearn's weighted k-means++ fit).
+    The O(N d trials) part of every step -- distances of all samples to the candidate rows, the minimum
     with the running closest distance, the candidates' potentials -- is one libofc launch (ofc_kpp_candidates); the
     RandomState draws, np.cumsum and searchsorted are numpy's, in sklearn's order.  -> (centres (k,d) f64 rows of X,
     indices).  The distances are not bit-identical to BLAS's (different summation order inside the dot product), so
@@ -90,7 +93,8 @@ def kmeans_plusplus(X, n_clusters, random_state=None, n_local_trials=None, devic
     if n_local_trials > 8:
         raise ValueError("n_local_trials > 8 is not supported")
     mean = X.astype(np.float64).mean(axis=0) if X.dtype != np.float32 else X.mean(axis=0).astype(np.float64)
-    weight = np.ones(N, np.float64)
+    w = _as_weights(sample_weight, N)
+    weight = np.ones(N, np.float64) if w is None else w.astype(np.float64)
     indices = np.full(n_clusters, -1, dtype=np.int64)
     indices[0] = rs.choice(N, p=weight / weight.sum())                            # :224
 
@@ -105,12 +109,15 @@ def kmeans_plusplus(X, n_clusters, random_state=None, n_local_trials=None, devic
         return out, pots
 
     out, pots = step(indices[:1], None)                                           # :233-236
-    closest, current_pot = out[0], pots[0]
+    closest, current_pot = out[0], pots[0] if w is None else out[0] @ weight
     for c in range(1, n_clusters):
         rand_vals = rs.uniform(size=n_local_trials) * current_pot                  # :242
-        candidate_ids = np.searchsorted(np.cumsum(closest, dtype=np.float64), rand_vals)   # :243-245
+        cum = np.cumsum(closest if w is None else weight * closest, dtype=np.float64)
+        candidate_ids = np.searchsorted(cum, rand_vals)                           # :243-245
         np.clip(candidate_ids, None, N - 1, out=candidate_ids)                    # :247
         out, pots = step(candidate_ids, closest)                                  # :250-256
+        if w is not None:
+            pots = out @ weight                                                   # :256
         best = int(np.argmin(pots))                                               # :259
         current_pot, closest = pots[best], out[best]
         indices[c] = candidate_ids[best]
@@ -142,21 +149,45 @@ def kpp_draws(rs, N, n_clusters, n_local_trials=None):
     return first, u, n_local_trials
 
 
+def kpp_draws_w(rs, n_clusters, n_local_trials=None):
+    """kpp_draws for the seeding with sample weights: the first centre is rs.choice(N, p=w / w.sum()), which consumes one
+    random_sample() whatever N is and returns searchsorted(cumsum(p), that number, side='right').  That number is handed
+    to the device, which looks it up in its own cumulative sum of the weights.
+    -> (u_first, u (n_clusters-1, n_local_trials), n_local_trials)"""
+    if n_local_trials is None:
+        n_local_trials = 2 + int(np.log(n_clusters))                              # :217-221
+    if n_local_trials > 8:
+        raise ValueError("n_local_trials > 8 is not supported")
+    u_first = float(rs.random_sample())
+    u = np.empty((n_clusters - 1, n_local_trials), np.float64)
+    for c in range(n_clusters - 1):
+        u[c] = rs.uniform(size=n_local_trials)
+    return u_first, u, n_local_trials
+
+
 def kmeans_plusplus_dev(X_ptr, dtype, N, d, n_clusters, random_state=None, n_local_trials=None, device=0,
-                        colsum=None, n_global=None):
+                        colsum=None, n_global=None, weights_ptr=None, weight_dtype=_lib.F32):
     """kmeans_plusplus on device-resident X (this rank's shard when a communicator is active: then n_global is the
     row count over all ranks, and every rank passes the same random_state).  The whole seeding runs in libofc
     (ofc_kpp_seed_dev): the closest distances stay on the device, each further centre costs one sweep over X.
-    The draws are kpp_draws'.  colsum as for kmeans_fit_dev.  -> (centres (k,d) f64 rows of X, GLOBAL indices)"""
+    The draws are kpp_draws'.  colsum as for kmeans_fit_dev.
+    weights_ptr: N device-resident sample weights of weight_dtype, as for kmeans_fit_dev: the seeding sklearn's
+    fit(X, sample_weight=) runs (ofc_kpp_seed_dev_w, draws: kpp_draws_w); None: unit weights.
+    -> (centres (k,d) f64 rows of X, GLOBAL indices)"""
     n_global = int(N if n_global is None else n_global)
     if n_global < 1:
         raise ValueError(f"n_samples={n_global} should be >= n_clusters={n_clusters}.")
-    first, u, n_local_trials = kpp_draws(check_random_state(random_state), n_global, int(n_clusters), n_local_trials)
     cs = np.ascontiguousarray(colsum, np.float64) if colsum is not None else None
     if cs is not None and cs.shape != (d,):
         raise ValueError(f"colsum must have shape ({d},)")
     centers = np.empty((n_clusters, d), np.float64)
     indices = np.empty(n_clusters, np.int64)
+    if weights_ptr:
+        u_first, u, n_local_trials = kpp_draws_w(check_random_state(random_state), int(n_clusters), n_local_trials)
+        check(load().ofc_kpp_seed_dev_w(device, C.c_void_p(X_ptr), dtype, C.c_void_p(weights_ptr), weight_dtype, N, d,
+                                        n_clusters, ptr(cs), u_first, ptr(u), n_local_trials, ptr(centers), ptr(indices)))
+        return centers, indices
+    first, u, n_local_trials = kpp_draws(check_random_state(random_state), n_global, int(n_clusters), n_local_trials)
     check(load().ofc_kpp_seed_dev(device, C.c_void_p(X_ptr), dtype, N, d, n_clusters, ptr(cs), first, ptr(u),
                                   n_local_trials, ptr(centers), ptr(indices)))
     return centers, indices
@@ -189,8 +220,9 @@ class KMeans:
             raise ValueError(f"n_samples={N} should be >= n_clusters={k}.")
         w = _as_weights(sample_weight, N)
         if w is not None and isinstance(self.init, str) and self.init == "k-means++":
-            raise ValueError("sample_weight together with init='k-means++' is not supported: the seeding on the device "
-                             "draws with unit weights (pass an explicit init or 'seeded-rows')")
+            raise ValueError("sample_weight together with init='k-means++' is not supported in one call (pass an "
+                             "explicit init or 'seeded-rows'; for sklearn's weighted seeding: C0, _ = kmeans_plusplus(X, k, "
+                             "random_state=s, sample_weight=w), then KMeans(k, init=C0).fit(X, sample_weight=w))")
         C0 = self._init_centers(X)          # 'seeded-rows' ignores the weights, as sklearn's array init does
         centers = np.empty((k, d), np.float64)
         labels = np.empty(N, np.int32)

@@ -719,8 +719,11 @@ int kpp_local_pots(LloydScratch &sc, int nblocks, double *pots8)
 }
 }  // namespace
 
-int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *colsum,
-                     int64_t first, const double *u, int n_trials, double *centers, int64_t *indices)
+namespace {
+// ofc_kpp_seed_dev (w_dev == nullptr: `first` is the first centre) and ofc_kpp_seed_dev_w (w_dev: u_first draws it)
+int kpp_seed(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d, int k,
+             const double *colsum, int64_t first, double u_first, const double *u, int n_trials, double *centers,
+             int64_t *indices)
 {
     OFC_REQUIRE(X_dev && centers && indices && (u || k == 1), "null pointer");
     OFC_REQUIRE(dtype >= OFC_U8 && dtype <= OFC_F64, "bad dtype %d", dtype);
@@ -730,6 +733,7 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
     for (int i = 0; i < (k - 1) * n_trials; i++)
         OFC_REQUIRE(u[i] >= 0.0 && u[i] < 1.0, "u[%d]=%g outside [0,1)", i, u[i]);
     OFC_REQUIRE(first >= 0, "first=%lld is negative", (long long)first);
+    OFC_REQUIRE(u_first >= 0.0 && u_first < 1.0, "u_first=%g outside [0,1)", u_first);
     if (N > KPP_NMAX) {
         set_error("N=%lld outside the seeding kernels' range (<= %lld samples per rank)", (long long)N, (long long)KPP_NMAX);
         return OFC_EUNSUPPORTED;
@@ -738,7 +742,7 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
     if (world > 64) { set_error("seeding over %d ranks is not supported (<= 64)", world); return OFC_EUNSUPPORTED; }
     if (world == 1) {       // with a communicator the same two tests follow the exchange of the shard sizes
         OFC_REQUIRE(N >= k, "n_samples=%lld should be >= n_clusters=%d.", (long long)N, k);
-        OFC_REQUIRE(first < N, "first=%lld outside 0..%lld", (long long)first, (long long)N - 1);
+        OFC_REQUIRE(w_dev || first < N, "first=%lld outside 0..%lld", (long long)first, (long long)N - 1);
     }
     OFC_TRY(ensure_device(device));
     LloydScratch &sc = scratch_for(device);
@@ -759,7 +763,7 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
         Ng += nq[q];
     }
     OFC_REQUIRE(Ng >= (double)k, "n_samples=%.0f should be >= n_clusters=%d.", Ng, k);
-    OFC_REQUIRE((double)first < Ng, "first=%lld outside 0..%.0f", (long long)first, Ng - 1);
+    OFC_REQUIRE(w_dev || (double)first < Ng, "first=%lld outside 0..%.0f", (long long)first, Ng - 1);
     if (nq[rank] != (double)N) { set_error("the communicator does not lay the shards out by rank"); return OFC_EUNSUPPORTED; }
 
     // ---- column mean, as the fit forms it ----
@@ -792,6 +796,53 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
     auto as_double = [&](const unsigned char *raw, int f) {
         return dtype == OFC_U8 ? (double)raw[f] : dtype == OFC_F32 ? (double)((const float *)raw)[f] : ((const double *)raw)[f];
     };
+    auto sweep = [&](const double *prev, int prev_mode, const double *cand, int n_cand) {
+        if (w_dev)
+            return launch_kpp_sweep_w(X_dev, dtype, w_dev, w_dtype, N, d, mean_h, prev, prev_mode, cand, n_cand, closest, cs,
+                                      sc.partial.as<double>(), nblocks, s);
+        return launch_kpp_sweep(X_dev, dtype, N, d, mean_h, prev, prev_mode, cand, n_cand, closest, cs,
+                                sc.partial.as<double>(), nblocks, s);
+    };
+
+    // ---- with weights, the first centre is drawn as RandomState.choice(N, p=w/w.sum()) draws it (_kmeans.py:224):
+    //      the smallest global row whose cumulative weight exceeds u_first * W ----
+    if (w_dev) {
+        pq[rank] = 0;
+        if (N > 0) {
+            OFC_TRY(launch_kpp_wchunks(w_dev, w_dtype, nullptr, N, cs, s));
+            OFC_TRY(launch_kpp_sum1024(cs, nchunks, ss, s));
+            OFC_TRY(launch_kpp_total(ss, (int)cdiv64(nchunks, 1024), sc.tot.as<double>(), s));
+            OFC_HIP(hipMemcpyAsync(&pq[rank], sc.tot.p, sizeof(double), hipMemcpyDeviceToHost, s));
+            OFC_HIP(hipStreamSynchronize(s));
+        }
+        OFC_TRY(kpp_exchange(sc, pq.data(), world, DIST_SUM));
+        double W = 0;
+        for (int q = 0; q < world; q++) W += pq[q];
+        if (!(W > 0)) { set_error("sum of sample weights must be positive"); return OFC_EINVAL; }
+        const double r = u_first * W;
+        // the first non-empty shard whose running sum exceeds r; the last one with any weight when rounding leaves none
+        int owner = -1;
+        double S = 0, base_me = 0;
+        for (int q = 0; q < world; q++) {
+            if (q == rank) base_me = S;
+            if (pq[q] > 0) {
+                owner = q;
+                if (S + pq[q] > r) break;
+            }
+            S += pq[q];
+        }
+        double gi = 0;
+        if (owner == rank) {
+            int64_t li;
+            OFC_TRY(launch_kpp_sample_w(X_dev, dtype, w_dev, w_dtype, N, d, mean_h, nullptr, KPP_PREV_NONE, nullptr, cs, ss,
+                                        &r, 1, base_me, KPP_SIDE_FIRST, idx_dev, rows_dev, s));
+            OFC_HIP(hipMemcpyAsync(&li, idx_dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            OFC_HIP(hipStreamSynchronize(s));
+            gi = off_me + (double)li;
+        }
+        OFC_TRY(kpp_exchange(sc, &gi, 1, DIST_BCAST));
+        first = (int64_t)gi;
+    }
 
     // ---- first centre: its owner broadcasts the row ----
     double rec[8 * (LLOYD_DMAX + 1)];
@@ -812,8 +863,7 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
     indices[0] = first;
     for (double &v : pl) v = 0;
     if (N > 0) {
-        OFC_TRY(launch_kpp_sweep(X_dev, dtype, N, d, mean_h, prev, KPP_PREV_FIRST, nullptr, 0, closest, cs,
-                                 sc.partial.as<double>(), nblocks, s));
+        OFC_TRY(sweep(prev, KPP_PREV_FIRST, nullptr, 0));
         OFC_TRY(launch_kpp_sum1024(cs, nchunks, ss, s));
         OFC_TRY(kpp_local_pots(sc, nblocks, pl));
     }
@@ -850,8 +900,14 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
         if (any) {
             int64_t idx_h[8];
             double rows_h[8 * LLOYD_DMAX];
-            OFC_TRY(launch_kpp_sample(X_dev, dtype, N, d, mean_h, prev, c >= 2 ? KPP_PREV_APPLY : KPP_PREV_NONE, closest,
-                                      cs + (size_t)slot * nchunks, ss, r, n_trials, base_me, idx_dev, rows_dev, s));
+            const int prev_mode = c >= 2 ? KPP_PREV_APPLY : KPP_PREV_NONE;
+            if (w_dev)
+                OFC_TRY(launch_kpp_sample_w(X_dev, dtype, w_dev, w_dtype, N, d, mean_h, prev, prev_mode, closest,
+                                            cs + (size_t)slot * nchunks, ss, r, n_trials, base_me, KPP_SIDE_LEFT, idx_dev,
+                                            rows_dev, s));
+            else
+                OFC_TRY(launch_kpp_sample(X_dev, dtype, N, d, mean_h, prev, prev_mode, closest,
+                                          cs + (size_t)slot * nchunks, ss, r, n_trials, base_me, idx_dev, rows_dev, s));
             OFC_HIP(hipMemcpyAsync(idx_h, idx_dev, sizeof(int64_t) * n_trials, hipMemcpyDeviceToHost, s));
             OFC_HIP(hipMemcpyAsync(rows_h, rows_dev, sizeof(double) * n_trials * LLOYD_DMAX, hipMemcpyDeviceToHost, s));
             OFC_HIP(hipStreamSynchronize(s));
@@ -869,8 +925,7 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
         // ---- one sweep: fold the previous winner into closest, evaluate the candidates (:250-256) ----
         for (double &v : pl) v = 0;
         if (N > 0) {
-            OFC_TRY(launch_kpp_sweep(X_dev, dtype, N, d, mean_h, prev, c >= 2 ? KPP_PREV_APPLY : KPP_PREV_NONE, cand,
-                                     n_trials, closest, cs, sc.partial.as<double>(), nblocks, s));
+            OFC_TRY(sweep(prev, c >= 2 ? KPP_PREV_APPLY : KPP_PREV_NONE, cand, n_trials));
             OFC_TRY(kpp_local_pots(sc, nblocks, pl));
         }
         memcpy(pg, pl, sizeof(pg));
@@ -889,6 +944,64 @@ int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d,
         indices[c] = (int64_t)rec[best * (d + 1) + d];
     }
     OFC_HIP(hipStreamSynchronize(s));
+    return OFC_OK;
+}
+
+int check_w_dtype(int w_dtype)
+{
+    if (w_dtype != OFC_F32 && w_dtype != OFC_F64) {
+        set_error("bad weight dtype %d (OFC_F32 or OFC_F64)", w_dtype);
+        return OFC_EINVAL;
+    }
+    return OFC_OK;
+}
+}  // namespace
+
+int ofc_kpp_seed_dev(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *colsum,
+                     int64_t first, const double *u, int n_trials, double *centers, int64_t *indices)
+{
+    return kpp_seed(device, X_dev, dtype, nullptr, OFC_F32, N, d, k, colsum, first, 0.0, u, n_trials, centers, indices);
+}
+
+int ofc_kpp_seed_dev_w(int device, const void *X_dev, int dtype, const void *w_dev, int w_dtype, int64_t N, int d, int k,
+                       const double *colsum, double u_first, const double *u, int n_trials, double *centers,
+                       int64_t *indices)
+{
+    OFC_REQUIRE(w_dev, "null weight pointer");
+    OFC_TRY(check_w_dtype(w_dtype));
+    OFC_REQUIRE((uintptr_t)w_dev % 16 == 0, "the weights must be 16-byte aligned");
+    return kpp_seed(device, X_dev, dtype, w_dev, w_dtype, N, d, k, colsum, 0, u_first, u, n_trials, centers, indices);
+}
+
+int ofc_kpp_sample_dev_w(int device, const void *w_dev, int w_dtype, const double *v_dev, int64_t N, const double *r, int n,
+                         int side, int64_t *idx, double *total)
+{
+    OFC_REQUIRE(w_dev && r && idx && total, "null pointer");
+    OFC_TRY(check_w_dtype(w_dtype));
+    OFC_REQUIRE((uintptr_t)w_dev % 16 == 0, "the weights must be 16-byte aligned");
+    OFC_REQUIRE(side == 0 || side == 1, "side %d: 0 (left) or 1 (right)", side);
+    OFC_REQUIRE(n >= 1 && n <= 8, "n %d outside 1..8", n);
+    OFC_REQUIRE(N >= 1, "N=%lld: nothing to sample from", (long long)N);
+    if (N > KPP_NMAX) {
+        set_error("N=%lld outside the seeding kernels' range (<= %lld samples)", (long long)N, (long long)KPP_NMAX);
+        return OFC_EUNSUPPORTED;
+    }
+    OFC_TRY(ensure_device(device));
+    const int64_t nchunks = kpp_chunks(N);
+    const int nsuper = (int)cdiv64(nchunks, 1024);
+    DevBuf cs, ss, out;
+    OFC_TRY(cs.alloc(sizeof(double) * (size_t)nchunks));
+    OFC_TRY(ss.alloc(sizeof(double) * (size_t)nsuper));
+    OFC_TRY(out.alloc(sizeof(int64_t) * 8 + sizeof(double)));
+    double *tot_dev = out.as<double>() + 8;
+    OFC_TRY(launch_kpp_wchunks(w_dev, w_dtype, v_dev, N, cs.as<double>(), nullptr));
+    OFC_TRY(launch_kpp_sum1024(cs.as<double>(), nchunks, ss.as<double>(), nullptr));
+    OFC_TRY(launch_kpp_total(ss.as<double>(), nsuper, tot_dev, nullptr));
+    OFC_TRY(launch_kpp_sample_w(nullptr, OFC_F64, w_dev, w_dtype, N, 1, nullptr, nullptr, KPP_PREV_NONE, v_dev, cs.as<double>(),
+                                ss.as<double>(), r, n, 0.0, side == 0 ? KPP_SIDE_LEFT : KPP_SIDE_RIGHT, out.as<int64_t>(),
+                                nullptr, nullptr));
+    OFC_HIP(hipMemcpy(idx, out.p, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    OFC_HIP(hipMemcpy(total, tot_dev, sizeof(double), hipMemcpyDeviceToHost));
     return OFC_OK;
 }
 
@@ -917,15 +1030,6 @@ int ofc_kpp_sample_dev(int device, const double *w_dev, int64_t N, const double 
 
 /* ---- sample weights, see include/ofc.h ---- */
 namespace {
-int check_w_dtype(int w_dtype)
-{
-    if (w_dtype != OFC_F32 && w_dtype != OFC_F64) {
-        set_error("bad weight dtype %d (OFC_F32 or OFC_F64)", w_dtype);
-        return OFC_EINVAL;
-    }
-    return OFC_OK;
-}
-
 // host weights: finite, non-negative, positive sum (sklearn's _check_sample_weight + the zero-sum refusal)
 int check_host_weights(const void *w, int w_dtype, int64_t N)
 {

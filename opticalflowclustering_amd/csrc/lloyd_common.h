@@ -115,6 +115,24 @@ int launch_kpp_sample(const void *X, int dtype, int64_t N, int d, const double *
                       const double *closest, const double *cs, const double *ss, const double *r, int n, double base,
                       int64_t *idx, double *rows, hipStream_t s);
 
+// the same with sample weights W (N of w_dtype, OFC_F32 / OFC_F64, 16-byte aligned): closest[] stays unweighted, every
+// sum is of w[i] * value[i] with the product rounded on its own
+int launch_kpp_sweep_w(const void *X, int dtype, const void *W, int w_dtype, int64_t N, int d, const double *mean,
+                       const double *prev, int prev_mode, const double *cand_centred, int n_cand, double *closest,
+                       double *cs, double *partial, int nblocks, hipStream_t s);
+// cs[kpp_chunks(N)] = per-chunk sums of (double)w[i] * v[i] (v == nullptr: of (double)w[i])
+int launch_kpp_wchunks(const void *W, int w_dtype, const double *v, int64_t N, double *cs, hipStream_t s);
+// total[0] = sum of ss[0..nsuper), nsuper <= 1024, in the order the sampling kernels accumulate it
+int launch_kpp_total(const double *ss, int nsuper, double *total, hipStream_t s);
+enum { KPP_SIDE_LEFT = 0,     // smallest i with cum[i] >= r, N - 1 when there is none (np.searchsorted, clipped)
+       KPP_SIDE_RIGHT = 1,    // smallest i with cum[i] >  r, N - 1 when there is none
+       KPP_SIDE_FIRST = 2 };  // the first centre: as RIGHT over rows of positive value only; when rounding leaves no
+                              // hit, the last row of positive value (RandomState.choice never returns a p = 0 row)
+// launch_kpp_sample over cum = base + cumsum(w * closest) (closest == nullptr: cumsum(w)), cs / ss its chunk sums
+int launch_kpp_sample_w(const void *X, int dtype, const void *W, int w_dtype, int64_t N, int d, const double *mean,
+                        const double *prev, int prev_mode, const double *closest, const double *cs, const double *ss,
+                        const double *r, int n, double base, int side, int64_t *idx, double *rows, hipStream_t s);
+
 // distributed plumbing (dist.cpp): no-ops when no communicator is set up
 bool dist_active();
 int dist_rank();

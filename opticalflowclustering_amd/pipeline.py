@@ -102,6 +102,26 @@ class ClipPipeline:
             self.weights.upload(w)
         return self.weights.ptr
 
+    def _colsum(self):
+        if not self._sums_valid:
+            return None
+        per_batch = self.uv_sums.download((self.n_batches, 2), np.float64)
+        colsum = np.zeros(2)
+        for b in range(self.n_batches):                 # fixed order
+            colsum += per_batch[b]
+        return colsum
+
+    def seed_kmeans(self, k, random_state=None, n_global=None, sample_weight=None):
+        """sklearn's k-means++ seeding on the resident (u,v) vectors (cluster.kmeans_plusplus_dev), with sample_weight as
+        in run_kmeans: the weights then decide the first centre, every later draw and every candidate's potential, as in
+        sklearn's fit(X, sample_weight=).  run_kmeans(C0, sample_weight=...) from the returned centres completes that fit.
+        None gives the seeds run_kmeans('k-means++', k=k) starts from.  -> (centers (k,2), GLOBAL indices)"""
+        self.sync()
+        N = self.n_pairs * self.W * self.H
+        wptr = self._weights_ptr(sample_weight, N)
+        return kmeans_plusplus_dev(self.flows.ptr, _lib.F32, N, 2, int(k), random_state, device=self.device,
+                                   colsum=self._colsum(), n_global=n_global, weights_ptr=wptr, weight_dtype=_lib.F32)
+
     def run_kmeans(self, init, max_iter=300, tol=1e-4, k=None, random_state=None, n_global=None, sample_weight=None):
         """Lloyd over all local (u,v) vectors (global when a communicator is active).
         init: (k,2) array, or 'k-means++' with k= and random_state=: sklearn's seeding on the resident vectors
@@ -109,18 +129,15 @@ class ClipPipeline:
         number of (u,v) vectors over all ranks.
         sample_weight: None, 'magnitude' (a vector counts by its length), ('moving', thr) (1 where the length reaches thr,
         else 0), or one value per local vector (kept as f32).  The weights live in a device buffer allocated on first use;
-        not available together with init='k-means++'.  -> centers (k,2), inertia, n_iter"""
+        not available together with init='k-means++' in one call (seed_kmeans(k, sample_weight=...) first, then pass its
+        centres as init).  -> centers (k,2), inertia, n_iter"""
         self.sync()
         N = self.n_pairs * self.W * self.H
         if sample_weight is not None and isinstance(init, str):
-            raise ValueError("sample_weight together with init='k-means++' is not supported (the seeding draws with unit weights)")
+            raise ValueError("sample_weight together with init='k-means++' is not supported in one call: seed first, "
+                             "C0, _ = seed_kmeans(k, random_state, sample_weight=...), then run_kmeans(C0, sample_weight=...)")
         wptr = self._weights_ptr(sample_weight, N)
-        colsum = None
-        if self._sums_valid:
-            per_batch = self.uv_sums.download((self.n_batches, 2), np.float64)
-            colsum = np.zeros(2)
-            for b in range(self.n_batches):                 # fixed order
-                colsum += per_batch[b]
+        colsum = self._colsum()
         if isinstance(init, str):
             if init != "k-means++" or k is None:
                 raise ValueError(f"init should be a (k,2) array or 'k-means++' together with k=, got {init!r}, k={k!r}")
