@@ -1172,6 +1172,9 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
     // UPS with the exact x2 pyramid: this thread's horizontal taps never change, and the 4 fine rows of a step touch only
     // 3 or 4 distinct coarse rows -- interpolate each coarse row once per step (the arithmetic of upsampled_flow, shared)
     constexpr bool ups2 = UPS == 2;
+    // the taps of the next step's two new coarse rows leave with this step's gathers (as fln does).  That keeps 8 more
+    // registers live across um_math, which M = 4 and 5 do not have (2 and 6 VGPRs would spill): there they leave after it
+    constexpr bool TAPS_EARLY = M != 4 && M != 5;
     int usx0 = 0, usx1 = 0;
     float ua1 = 0.f;
     if (ups2) {
@@ -1193,10 +1196,15 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
         const float a0 = 1.f - ua1;
         return make_float2(p0.x * a0 + p1.x * ua1, p0.y * a0 + p1.y * ua1);
     };
+    auto coarse_vert = [&](float2 h0, float2 h1, float b1) -> float2 {  // vertical interpolation of upsampled_flow, times mul
+#pragma clang fp contract(off)
+        const float b0 = 1.f - b1;
+        return make_float2((h0.x * b0 + h1.x * b1) * ups.mul, (h0.y * b0 + h1.y * b1) * ups.mul);
+    };
     // consecutive steps advance by two coarse rows: rows s0+2, s0+3 of a step are rows s0, s0+1 of the next (carried,
-    // interpolated), and the taps of the next step's two new rows are requested behind this step's gathers so that they
-    // travel during the horizontal pass, like the flow vectors of the non-UPS form
-    float2 hcar[2], pn[2][2];
+    // interpolated), and the taps of the next step's two new rows are requested one step ahead, like the flow vectors of the
+    // non-UPS form, and interpolated (hnx) BEFORE the step's stores are issued (see "retire" below)
+    float2 hcar[2], hnx[2], pn[2][2];
     bool have_next = false;
     float2 fl_last = ups2 ? flow_at(H - 1) : make_float2(0.f, 0.f);   // flow of the last image row this thread has seen
 
@@ -1211,8 +1219,25 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
         float2 fl[BS_ROWS];
         UmIn u[BS_ROWS];
         __builtin_amdgcn_s_setprio(3);
+        if (ups2) {
+            // the 16 taps of the group's four rows leave together, outside any branch (flow_at compiles to loads inside
+            // divergent branches: one round trip per row); the arithmetic is upsampled_flow's exact-x2 case
+            float2 tp[BS_ROWS][4];
 #pragma unroll
-        for (int q = 0; q < BS_ROWS; q++) fl[q] = flow_at(min(max(y_begin + j4 + q, 0), H - 1));
+            for (int q = 0; q < BS_ROWS; q++) {
+                const int sy = (min(max(y_begin + j4 + q, 0), H - 1) + 1) / 2 - 1;
+                coarse_taps(sy, tp[q][0], tp[q][1]);
+                coarse_taps(sy + 1, tp[q][2], tp[q][3]);
+            }
+#pragma unroll
+            for (int q = 0; q < BS_ROWS; q++) {
+                const int row = min(max(y_begin + j4 + q, 0), H - 1);
+                fl[q] = coarse_vert(coarse_lerp(tp[q][0], tp[q][1]), coarse_lerp(tp[q][2], tp[q][3]), (row & 1) ? 0.25f : 0.75f);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < BS_ROWS; q++) fl[q] = flow_at(min(max(y_begin + j4 + q, 0), H - 1));
+        }
 #pragma unroll
         for (int q = 0; q < BS_ROWS; q++)
             um_load(R0, R1, plane, W, H, xc, min(max(y_begin + j4 + q, 0), H - 1), fl[q], u[q]);
@@ -1233,8 +1258,8 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
     }
 
     // the flow vectors steer the gather addresses: fetched one step ahead (behind the current step's gathers) so that a
-    // step does not start with a second, dependent memory round trip.  (UPS computes them from 4 coarse taps: not
-    // worth 16 more loads in flight.)
+    // step does not start with a second, dependent memory round trip.  (UPS 1 computes them from 4 coarse taps: not
+    // worth 16 more loads in flight; UPS 2 carries interpolated coarse rows instead, see hcar / hnx.)
     float2 fln[BS_ROWS];
     if (!UPS) {
 #pragma unroll
@@ -1249,6 +1274,16 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
             if (slot >= 0) acc_t[slot] += t - tprev;
             tprev = t;
         }
+    };
+    auto request_next = [&](int yc) {       // taps of coarse rows s0'+2, s0'+3 of the step after the one at yc
+        const int s0n = (yc + BS_ROWS + 1 + M + 1) / 2 - 1;
+        coarse_taps(s0n + 2, pn[0][0], pn[0][1]);
+        coarse_taps(s0n + 3, pn[1][0], pn[1][1]);
+    };
+    auto retire_next = [&]() {
+        hnx[0] = coarse_lerp(pn[0][0], pn[0][1]);
+        hnx[1] = coarse_lerp(pn[1][0], pn[1][1]);
+        asm volatile("" : "+v"(hnx[0].x), "+v"(hnx[0].y), "+v"(hnx[1].x), "+v"(hnx[1].y));
     };
     stamp(-1);
     for (int y16 = y_begin; y16 < y_end; y16 += 16) {
@@ -1266,8 +1301,8 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
                     if (have_next) {                            // uniform
                         hc[0] = hcar[0];
                         hc[1] = hcar[1];
-                        hc[2] = coarse_lerp(pn[0][0], pn[0][1]);
-                        hc[3] = coarse_lerp(pn[1][0], pn[1][1]);
+                        hc[2] = hnx[0];
+                        hc[3] = hnx[1];
                     } else {
 #pragma unroll
                         for (int j = 0; j < BS_ROWS; j++) {
@@ -1299,8 +1334,12 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
                 {
                     UmIn u[BS_ROWS];
                     // a wave that is ready to issue its gathers goes first: while its SIMD neighbour grinds through a
-                    // horizontal pass, all 36 requests of this step leave at once instead of trickling out between the
-                    // neighbour's VALU instructions (level-0 launch 783 -> 655 us)
+                    // horizontal pass, the requests of this step (32 gathers + 4 flow vectors or coarse taps) leave back to
+                    // back instead of trickling out between the neighbour's VALU instructions (level-0 launch 783 -> 655 us).
+                    // No s_waitcnt vmcnt sits among them: everything they depend on was retired before the previous step's
+                    // stores ("retire" below; tools/waitcnt_listing.py shows the sequence).  UPS 1 keeps its dependent fetch
+                    // here, and the first of the four unrolled steps keeps the wait of the way in from the front of the loop
+                    // 
                     stamp(0);                                   // 0: loop head, flow vectors / coarse taps of this step
                     __builtin_amdgcn_s_setprio(3);
 #pragma unroll
@@ -1311,6 +1350,7 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
                         for (int r = 0; r < BS_ROWS; r++)
                             fln[r] = flow_in[(size_t)min(yc + BS_ROWS + r + 1 + M, H - 1) * W + xc];
                     }
+                    if (ups2 && TAPS_EARLY) request_next(yc);
                     stamp(1);                                   // 1: issuing the gathers
                     if (STAMP) {
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1323,11 +1363,7 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
                     for (int r = 0; r < BS_ROWS; r++)
                         um_math(u[r], W, H, xc, min(yc + r + 1 + M, H - 1), fl[r], mi[r]);
                 }
-                if (ups2) {                 // taps of coarse rows s0'+2, s0'+3 of the next step (the gathered operands are dead now)
-                    const int s0n = (yc + BS_ROWS + 1 + M + 1) / 2 - 1;
-                    coarse_taps(s0n + 2, pn[0][0], pn[0][1]);
-                    coarse_taps(s0n + 3, pn[1][0], pn[1][1]);
-                }
+                if (ups2 && !TAPS_EARLY) request_next(yc);     // (the gathered operands are dead now)
                 stamp(7);                                       // 7: matrix arithmetic
                 // the barrier that protects `vs` from the previous step's readers sits HERE, after this step's loads and
                 // matrix arithmetic: a wave that finished its horizontal pass early starts its gathers without waiting
@@ -1348,6 +1384,14 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
                 __syncthreads();
                 stamp(5);                                       // 5: second barrier
                 __builtin_amdgcn_s_setprio(0);
+                // retire: what was prefetched for the next step becomes register values HERE, before this step's stores are
+                // issued.  A store is counted in vmcnt like a load and the counter retires in order: left to the next loop
+                // head, the wait for these operands would also wait for the stores issued after them
+                if (!UPS) {
+#pragma unroll
+                    for (int r = 0; r < BS_ROWS; r++) asm volatile("" : "+v"(fln[r].x), "+v"(fln[r].y));
+                }
+                if (ups2) retire_next();
                 const int y = yc + wave;
                 const int xo = x0 + 4 * lane;
                 if (y < y_end && 4 * lane < TXO && xo < W) {
@@ -1378,19 +1422,31 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
                         const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
                         fo[o] = make_float2((float)((g11 * h2 - g12 * h1) * idet), (float)((g22 * h1 - g12 * h2) * idet));
                     }
-                    if (SUMS) {
-#pragma unroll
-                        for (int o = 0; o < 4; o++)
-                            if (4 * lane + o < TXO && xo + o < W) { su += (double)fo[o].x; sv += (double)fo[o].y; }
-                    }
                     float2 *dst = flow_out + (size_t)y * W + xo;
                     if (4 * lane + 3 < TXO && xo + 3 < W && (W & 1) == 0) {      // 32 contiguous, 16-B aligned bytes
-                        reinterpret_cast<float4 *>(dst)[0] = make_float4(fo[0].x, fo[0].y, fo[1].x, fo[1].y);
-                        reinterpret_cast<float4 *>(dst)[1] = make_float4(fo[2].x, fo[2].y, fo[3].x, fo[3].y);
+                        // both 16-byte vectors are formed before either is stored: two stores (left alone, the compiler
+                        // shares the store of the fourth vector with the per-pixel path and issues 16 + 8 + 8 bytes)
+                        typedef float f4v __attribute__((ext_vector_type(4)));
+                        f4v o0 = {fo[0].x, fo[0].y, fo[1].x, fo[1].y}, o1 = {fo[2].x, fo[2].y, fo[3].x, fo[3].y};
+                        asm volatile("" : "+v"(o0), "+v"(o1));
+                        reinterpret_cast<f4v *>(dst)[0] = o0;
+                        reinterpret_cast<f4v *>(dst)[1] = o1;
+                        // behind the stores and inside the branch: in front of it the sums cost the registers of the two
+                        // tuples (the form spilled).  All four vectors are inside the tile and the image here; same order
+                        // of additions as below
+                        if (SUMS) {
+                            su += (double)o0.x; sv += (double)o0.y;
+                            su += (double)o0.z; sv += (double)o0.w;
+                            su += (double)o1.x; sv += (double)o1.y;
+                            su += (double)o1.z; sv += (double)o1.w;
+                        }
                     } else {
 #pragma unroll
                         for (int o = 0; o < 4; o++)
-                            if (4 * lane + o < TXO && xo + o < W) dst[o] = fo[o];
+                            if (4 * lane + o < TXO && xo + o < W) {
+                                dst[o] = fo[o];
+                                if (SUMS) { su += (double)fo[o].x; sv += (double)fo[o].y; }
+                            }
                     }
                 }
                 stamp(6);                                       // 6: horizontal sums + solve + stores
