@@ -420,6 +420,22 @@ void ofc_stream_destroy(ofc_stream_t *s);
 /* per-cell mean of a flow field (host buffers): flow HxWx2 f32 -> cell_uv rows*cols x 2 f32 */
 int ofc_grid_cell_mean_flow(int device, const float *flow, int W, int H, int rows, int cols, float *cell_uv);
 
+/* Per grid cell and label: how many pixels carry it, and optionally the sums of their flow vectors.
+ * Grid geometry is overlayGridAndComputeAvgColor's (KmeanGrids.py:56-59), as k_grid_cell_mean_flow uses it:
+ * xs = W / cols, ys = H / rows; cell cy*cols+cx owns rows [cy*ys, (cy+1)*ys) x columns [cx*xs, (cx+1)*xs).
+ * Pixels right of cols*xs or below rows*ys belong to no cell.
+ * labels_dev  n_frames x H x W u8 (what ofc_kmeans_fit_dev leaves in labels_dev for n_frames flow fields).
+ *             A label >= k (0xFF = unassigned included) is counted nowhere and indexes nothing.
+ * counts_dev  n_frames x rows*cols x k int32
+ * flow_dev, sums_dev: both NULL, or flow_dev n_frames x H x W x 2 f32 and sums_dev n_frames x rows*cols x k x 2 f64
+ *             = sum of u, sum of v over the pixels counted (f64 accumulation in a fixed order: two calls give the same
+ *             bits, and a frame's sums do not depend on n_frames; +0.0 where the count is 0).
+ * OFC_EINVAL: null pointers, only one of flow_dev / sums_dev, n_frames < 1, rows < 1 or > H, cols < 1 or > W.
+ * OFC_EUNSUPPORTED: k outside 1 .. 16 (LLOYD_KMAX); W*H above 2^31 - 1.  Everything is checked before anything is
+ * launched. */
+int ofc_grid_label_counts_dev(int device, const uint8_t *labels_dev, const float *flow_dev, int W, int H,
+                              int n_frames, int rows, int cols, int k, int32_t *counts_dev, double *sums_dev);
+
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.

@@ -111,6 +111,7 @@ _PROTOS = {
     "ofc_stream_finish": ([_vp, _vp, _i, _ip], _i),
     "ofc_stream_destroy": ([_vp], None),
     "ofc_grid_cell_mean_flow": ([_i, _vp, _i, _i, _i, _i, _vp], _i),
+    "ofc_grid_label_counts_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

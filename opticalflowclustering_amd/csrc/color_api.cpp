@@ -191,6 +191,27 @@ int ofc_grid_kmeans(int device, const uint8_t *bgr, int W, int H, int rows, int 
                                channel_order, centers, hsv);
 }
 
+int ofc_grid_label_counts_dev(int device, const uint8_t *labels_dev, const float *flow_dev, int W, int H, int n_frames,
+                              int rows, int cols, int k, int32_t *counts_dev, double *sums_dev)
+{
+    OFC_REQUIRE(labels_dev && counts_dev, "null pointer");
+    OFC_REQUIRE(!flow_dev == !sums_dev, "flow_dev and sums_dev go together: both or neither");
+    OFC_REQUIRE(n_frames >= 1 && W >= 1 && H >= 1, "bad size %dx%d x %d frames", W, H, n_frames);
+    OFC_REQUIRE(rows >= 1 && cols >= 1 && W >= cols && H >= rows, "grid %dx%d does not fit %dx%d", rows, cols, W, H);
+    if (k < 1 || k > LLOYD_KMAX) {
+        set_error("k=%d outside the kernel's range (1..%d)", k, LLOYD_KMAX);
+        return OFC_EUNSUPPORTED;
+    }
+    if ((int64_t)W * H > INT32_MAX) {          // a cell's pixels are numbered in 32 bits
+        set_error("frames of %dx%d pixels are not supported (more than 2^31 - 1)", W, H);
+        return OFC_EUNSUPPORTED;
+    }
+    OFC_TRY(ensure_device(device));
+    OFC_TRY(launch_grid_label_counts(labels_dev, flow_dev, W, H, n_frames, rows, cols, k, counts_dev, sums_dev, nullptr));
+    OFC_HIP(hipStreamSynchronize(nullptr));
+    return OFC_OK;
+}
+
 int ofc_sliding_cosine(int device, const double *small_v, int n_small, const double *large_v, int n_large, double *sims)
 {
     OFC_REQUIRE(small_v && large_v && sims, "null pointer");

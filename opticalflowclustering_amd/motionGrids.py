@@ -1,0 +1,145 @@
+"""The clip-wide motion fit as a table: one row per frame pair, one value per cell of the 14 x 25 grid, in the format of
+KmeanGrids.process_video's hue CSV (which findCosineDifferentVectors.py compares column by column).
+
+A clip's (u,v) vectors are clustered over the whole clip (ClipPipeline.run_kmeans), or labelled against the centres of
+another clip's fit (ClipPipeline.assign), and ClipPipeline.cell_clusters() counts on the device how many pixels of every
+cell fall into every cluster.  A cell's value is its dominant cluster, written as the hue the reference's colour coding
+gives that cluster's direction (computeOpticalFlowModule.py:25-33: hue = angle / 2), or as the cluster index.
+
+    python -m opticalflowclustering_amd.motionGrids --path CLIP -c 5 -f OUT.csv --save-model centres.npy
+    python -m opticalflowclustering_amd.motionGrids --path OTHER -c 5 -f OTHER.csv --model centres.npy
+"""
+import argparse
+import os
+
+import numpy as np
+
+
+def dominant(counts):
+    """the cluster with the most pixels per cell: the first maximum, so ties (an empty cell included) go to the lowest
+    cluster index.  counts (..., k) -> (...)"""
+    return np.argmax(np.asarray(counts), axis=-1)
+
+
+def centre_hues(centers):
+    """the hue (0..179) flow_to_bgr paints a centre's direction with: its angle in degrees, halved and truncated.
+    (0, 0) has angle 0; an angle that rounds up to 360 wraps to hue 0.  centers (k,2) -> (k,) int64"""
+    cen = np.asarray(centers, np.float64).reshape(-1, 2)
+    return np.array([int(np.degrees(np.arctan2(v, u)) % 360.0 / 2.0) % 180 for u, v in cen], np.int64)
+
+
+def hue_rows(counts, centers):
+    """counts (n, cells, k), centers (k,2) -> (n, cells) int64: the hue of every cell's dominant cluster"""
+    counts = np.asarray(counts)
+    hues = centre_hues(centers)
+    if counts.shape[-1] != len(hues):
+        raise ValueError(f"counts are over {counts.shape[-1]} clusters, centers has {len(hues)}")
+    return hues[dominant(counts)]
+
+
+def write_csv(path, rows):
+    """header cell_0 .. cell_{n-1}, then one comma-separated line of integers per row (KmeanGrids.py:394-399)"""
+    rows = np.asarray(rows)
+    if rows.ndim != 2:
+        raise ValueError(f"rows must be (n, cells), got shape {rows.shape}")
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+        f.write(",".join(f"cell_{i}" for i in range(rows.shape[1])) + "\n")
+        for r in rows:
+            f.write(",".join(str(int(h)) for h in r) + "\n")
+
+
+def parse_weights(text):
+    """'none' -> None, 'magnitude' -> 'magnitude', 'moving:THR' -> ('moving', THR): ClipPipeline's sample_weight"""
+    if text == "none":
+        return None
+    if text == "magnitude":
+        return "magnitude"
+    kind, _, thr = text.partition(":")
+    if kind == "moving" and thr:
+        try:
+            return ("moving", float(thr))
+        except ValueError:
+            pass
+    raise argparse.ArgumentTypeError(f"weights should be none, magnitude or moving:THR, got {text!r}")
+
+
+def parse_arguments(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m opticalflowclustering_amd.motionGrids", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--path", required=True, help="input video (.npy/.npz stack, image directory, or a video with cv2)")
+    ap.add_argument("-c", "--clusters", required=True, type=int, help="number of motion clusters")
+    ap.add_argument("-f", "--csv", required=True, help="output table: one row per frame pair, one column per cell")
+    ap.add_argument("--rows", type=int, default=14)
+    ap.add_argument("--cols", type=int, default=25)
+    ap.add_argument("--init", default="k-means++", help="k-means++ or a .npy file with (k,2) initial centres")
+    ap.add_argument("--seed", type=int, default=0, help="random_state of the k-means++ seeding")
+    ap.add_argument("--weights", type=parse_weights, default=None, metavar="none|magnitude|moving:THR",
+                    help="sample weights of the fit")
+    ap.add_argument("--model", help=".npy file with (k,2) centres: label against them instead of fitting")
+    ap.add_argument("--save-model", help="write the centres used (fitted or given) to this .npy file")
+    ap.add_argument("--counts", help="write the (pairs, cells, k) pixel counts to this .npy file")
+    ap.add_argument("--value", choices=("hue", "label"), default="hue",
+                    help="a cell's value: the hue of its dominant cluster's direction, or that cluster's index")
+    ap.add_argument("--device", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def _load_centres(path, k, what):
+    cen = np.asarray(np.load(path), np.float64)
+    if cen.shape != (k, 2):
+        raise ValueError(f"{what} {path!r} holds an array of shape {cen.shape}, expected ({k}, 2)")
+    return cen
+
+
+def read_gray_frames(path, device=0):
+    """every frame of the clip as (T, H, W) u8 grey (cv2's BGR2GRAY, on the device, for three-channel frames)"""
+    from .frameio import FrameSource
+    from .vis import bgr2gray
+    cap = FrameSource(path)
+    frames = []
+    while cap.isOpened():
+        ret, frame = cap.read()
+        if not ret:
+            break
+        frames.append(bgr2gray(frame, device) if frame.ndim == 3 else np.ascontiguousarray(frame, np.uint8))
+    cap.release()
+    if len(frames) < 2:
+        raise RuntimeError(f"{path!r} has {len(frames)} frame(s); a flow field needs two")
+    return np.stack(frames)
+
+
+def main(argv=None):
+    args = parse_arguments(argv)
+    from .pipeline import ClipPipeline
+    k = args.clusters
+    given = _load_centres(args.model, k, "--model") if args.model else \
+        _load_centres(args.init, k, "--init") if args.init != "k-means++" else None
+    frames = read_gray_frames(args.path, args.device)
+    T, H, W = frames.shape
+    pipe = ClipPipeline(W, H, T, device=args.device)
+    try:
+        pipe.upload_frames(frames)
+        pipe.run_flow()
+        if args.model:
+            centers = given
+            pipe.assign(centers)
+        elif given is not None:
+            centers, _, _ = pipe.run_kmeans(given, sample_weight=args.weights)
+        elif args.weights is not None:          # sklearn's weighted k-means++ fit in its two-step form
+            C0, _ = pipe.seed_kmeans(k, args.seed, sample_weight=args.weights)
+            centers, _, _ = pipe.run_kmeans(C0, sample_weight=args.weights)
+        else:
+            centers, _, _ = pipe.run_kmeans("k-means++", k=k, random_state=args.seed)
+        counts = pipe.cell_clusters(args.rows, args.cols)
+    finally:
+        pipe.close()
+    write_csv(args.csv, hue_rows(counts, centers) if args.value == "hue" else dominant(counts))
+    if args.save_model:
+        np.save(args.save_model, centers)
+    if args.counts:
+        np.save(args.counts, counts)
+    return counts, centers
+
+
+if __name__ == "__main__":
+    main()

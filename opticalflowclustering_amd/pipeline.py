@@ -55,6 +55,7 @@ class ClipPipeline:
         self.uv_sums = DeviceBuffer(self.n_batches * 16, device)
         self._sums_valid = False
         self.weights = None                 # N f32 sample weights for run_kmeans, allocated on first use
+        self._label_k = None                # the k the resident labels were written with (run_kmeans / assign), or None
 
     def synth(self, t0=0, seed=0):
         """fill the resident clip with synthetic frames t0 .. t0+n_frames-1"""
@@ -75,6 +76,7 @@ class ClipPipeline:
                                                                 uv_sum_ptr=self.uv_sums.ptr + 16 * i if stats else None)
             p0 += n
         self._sums_valid = stats
+        self._label_k = None                # the labels belong to the field that was just overwritten
         if sync:
             self.sync()
 
@@ -143,8 +145,57 @@ class ClipPipeline:
                 raise ValueError(f"init should be a (k,2) array or 'k-means++' together with k=, got {init!r}, k={k!r}")
             init, _ = kmeans_plusplus_dev(self.flows.ptr, _lib.F32, N, 2, int(k), random_state, device=self.device,
                                           colsum=colsum, n_global=n_global)
-        return kmeans_fit_dev(self.flows.ptr, _lib.F32, N, 2, init, max_iter, tol, self.labels.ptr, self.device, colsum=colsum,
-                              weights_ptr=wptr, weight_dtype=_lib.F32)
+        self._label_k = None
+        fit = kmeans_fit_dev(self.flows.ptr, _lib.F32, N, 2, init, max_iter, tol, self.labels.ptr, self.device, colsum=colsum,
+                             weights_ptr=wptr, weight_dtype=_lib.F32)
+        self._label_k = len(fit[0])
+        return fit
+
+    def assign(self, centers):
+        """label the resident (u,v) vectors against the given (k,2) centres without fitting (a model fitted on another
+        clip, say): one E-step (ofc_lloyd_step_dev, nothing accumulated), centred by this field's own column mean as the
+        fit's final E-step is.  The labels replace the resident ones; cell_clusters() summarises them.  Under a
+        communicator this is rank-local: this rank's pairs, this rank's mean, no collective."""
+        self.sync()
+        cen = np.ascontiguousarray(centers, np.float64)
+        if cen.ndim != 2 or cen.shape[1] != 2 or len(cen) < 1:
+            raise ValueError(f"centers should be a (k,2) array, got shape {cen.shape}")
+        N = self.n_pairs * self.W * self.H
+        colsum = self._colsum()
+        if colsum is None:
+            colsum = np.empty(2, np.float64)
+            check(load().ofc_lloyd_colstats_dev(self.device, C.c_void_p(self.flows.ptr), _lib.F32, N, 2, None, 0,
+                                                _lib.ptr(colsum)))
+        mean = np.ascontiguousarray(colsum / N)
+        self._label_k = None
+        check(load().ofc_lloyd_step_dev(self.device, C.c_void_p(self.flows.ptr), _lib.F32, N, 2, len(cen), _lib.ptr(mean),
+                                        _lib.ptr(np.ascontiguousarray(cen - mean)), C.c_void_p(self.labels.ptr), 0, None))
+        self._label_k = len(cen)
+
+    def cell_clusters(self, rows=14, cols=25, sums=False):
+        """what the resident labels say per grid cell (ofc_grid_label_counts_dev, the grid of KmeanGrids.py:56-59):
+        counts (n_pairs, rows*cols, k) int32 = pixels of the cell in each cluster, and with sums=True also
+        (n_pairs, rows*cols, k, 2) f64 = the sums of their (u, v); only these few numbers leave the device.
+        Needs labels: after run_kmeans() or assign(), not after a run_flow() that replaced the field.
+        Under a communicator the result covers this rank's pairs; the ranks' rows concatenated in rank order are the
+        single-rank result (a pair's rows depend on that pair alone), so no collective is involved."""
+        if self._label_k is None:
+            raise ValueError("cell_clusters needs labels for the resident field: call run_kmeans() or assign() first "
+                             "(run_flow() discards them)")
+        k, n = self._label_k, self.n_pairs
+        nout = max(n * int(rows) * int(cols) * k, 1)      # the library refuses a grid that does not fit
+        cnt = DeviceBuffer(nout * 4, self.device)
+        sm = DeviceBuffer(nout * 16, self.device) if sums else None
+        try:
+            check(load().ofc_grid_label_counts_dev(self.device, C.c_void_p(self.labels.ptr),
+                                                   C.c_void_p(self.flows.ptr) if sums else None, self.W, self.H, n, rows, cols,
+                                                   k, C.c_void_p(cnt.ptr), C.c_void_p(sm.ptr) if sums else None))
+            counts = cnt.download((n, rows * cols, k), np.int32)
+            return (counts, sm.download((n, rows * cols, k, 2), np.float64)) if sums else counts
+        finally:
+            cnt.free()
+            if sm is not None:
+                sm.free()
 
     def sample_uv(self, idx):
         """host copy of a few (u,v) rows (for choosing the initial centres)"""

@@ -65,6 +65,38 @@ def grid_cell_means(bgr, rows=14, cols=25, device=0):
     return mean, hsv
 
 
+def grid_label_counts(labels, k, rows=14, cols=25, flow=None, device=0):
+    """per frame, grid cell and cluster: how many of the cell's pixels carry the label, and with `flow` the sums of their
+    (u, v) (ofc_grid_label_counts_dev; the grid is overlayGridAndComputeAvgColor's, remainder pixels belong to no cell;
+    labels >= k are counted nowhere).  labels (n, H, W) or (H, W) u8, flow (n, H, W, 2) or (H, W, 2) f32
+    -> counts (n, rows*cols, k) int32, or (counts, sums (n, rows*cols, k, 2) f64) when a flow is given"""
+    labels = np.ascontiguousarray(labels, np.uint8)
+    if labels.ndim == 2:
+        labels = labels[None]
+    if labels.ndim != 3:
+        raise ValueError(f"labels must be (n, H, W) or (H, W), got shape {labels.shape}")
+    n, H, W = labels.shape
+    if flow is not None:
+        flow = np.ascontiguousarray(flow, np.float32)
+        if flow.ndim == 3:
+            flow = flow[None]
+        if flow.shape != (n, H, W, 2):
+            raise ValueError(f"flow must be {(n, H, W, 2)} to go with the labels, got {flow.shape}")
+    k, rows, cols = int(k), int(rows), int(cols)
+    nout = max(n * rows * cols * k, 1)                # the library refuses a bad k / rows / cols; nothing is read back then
+    bufs = [DeviceBuffer(max(labels.nbytes, 1), device).upload(labels), DeviceBuffer(nout * 4, device)]
+    try:
+        if flow is not None:
+            bufs += [DeviceBuffer(max(flow.nbytes, 1), device).upload(flow), DeviceBuffer(nout * 16, device)]
+        check(load().ofc_grid_label_counts_dev(device, bufs[0].ptr, bufs[2].ptr if flow is not None else None, W, H, n,
+                                               rows, cols, k, bufs[1].ptr, bufs[3].ptr if flow is not None else None))
+        counts = bufs[1].download((n, rows * cols, k), np.int32)
+        return counts if flow is None else (counts, bufs[3].download((n, rows * cols, k, 2), np.float64))
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def kmeans_fit_batched(X, offsets, k, init=None, max_iter=300, tol=1e-4, device=0):
     """many independent u8 RGBA problems in one launch.
     -> centers (P,k,4) f64, counts (P,k) = bincount(predict), labels (total,), n_iter (P,)"""
