@@ -416,6 +416,21 @@ int ofc_stream_push_gray(ofc_stream_t *s, const uint8_t *gray, int *pairs_done);
  * before pushing further frames).
  * cell_uv == NULL: count only; *n_pairs is set and the results are dropped. */
 int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pairs);
+/* A stream that also counts: from the next batch on, every pair's field is labelled against the model and counted per
+ * cell (ofc_grid_assign_counts_dev's kernel, behind the cell means of the same batch, so *pairs_done keeps its meaning).
+ * mean: 2 doubles, NULL = (0, 0); centers_c: k x 2, the centres minus mean, as for ofc_lloyd_step_dev.  A stream has no
+ * field mean before its clip ends, so the usual model is mean (0, 0): KMeans.predict's un-centred E-step.
+ * Only on a stream that holds no frame and no undelivered result (fresh, or straight after a finish): otherwise OFC_EINVAL
+ * and the model stays as it was.  k outside 0 .. 16: OFC_EUNSUPPORTED; a mean or centre that is not finite: OFC_EINVAL.
+ * k = 0 removes the model: the stream then launches exactly what a stream that never had one launches. */
+int ofc_stream_set_model(ofc_stream_t *s, int k, const double *mean, const double *centers_c, int with_sums);
+/* ofc_stream_finish that also delivers counts[n_pairs][rows*cols][k] int32 (and sums[n_pairs][rows*cols][k][2] f64 when the
+ * model was set with_sums), as ofc_grid_assign_counts_dev writes them for each pair's field.
+ * cell_uv, counts, sums may each be NULL (not copied; all NULL: count and drop).  Too small: exactly ofc_stream_finish's
+ * contract (OFC_EINVAL, *n_pairs set, nothing written, results stay).
+ * OFC_EINVAL without a model, or with sums != NULL on a model without sums.
+ * ofc_stream_finish on a stream with a model returns the cell means as ever and drops the counts. */
+int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts, double *sums, int max_pairs, int *n_pairs);
 void ofc_stream_destroy(ofc_stream_t *s);
 /* per-cell mean of a flow field (host buffers): flow HxWx2 f32 -> cell_uv rows*cols x 2 f32 */
 int ofc_grid_cell_mean_flow(int device, const float *flow, int W, int H, int rows, int cols, float *cell_uv);
@@ -435,6 +450,16 @@ int ofc_grid_cell_mean_flow(int device, const float *flow, int W, int H, int row
  * launched. */
 int ofc_grid_label_counts_dev(int device, const uint8_t *labels_dev, const float *flow_dev, int W, int H,
                               int n_frames, int rows, int cols, int k, int32_t *counts_dev, double *sums_dev);
+/* ofc_lloyd_step_dev's label (accumulate = 0) of every pixel's (u,v), counted as ofc_grid_label_counts_dev counts labels, in
+ * one sweep and without a label buffer: 8 B read and nothing written per pixel.  The label is the byte ofc_lloyd_step_dev
+ * writes for the same pixel, mean and centres (one shared device function); counts and sums are then those of
+ * ofc_grid_label_counts_dev on these labels, bit for bit (same walk, same order of summation).
+ * mean: 2 doubles (host), NULL = (0, 0); centers_c: k x 2 (host), the centres minus mean, as for ofc_lloyd_step_dev.
+ * sums_dev may be NULL.
+ * OFC_EINVAL: null pointers, a mean or centre that is not finite, n_frames < 1, rows < 1 or > H, cols < 1 or > W.
+ * OFC_EUNSUPPORTED: k outside 1 .. 16; W*H above 2^31 - 1.  Everything is checked before anything is launched. */
+int ofc_grid_assign_counts_dev(int device, const float *flow_dev, int W, int H, int n_frames, int rows, int cols, int k,
+                               const double *mean, const double *centers_c, int32_t *counts_dev, double *sums_dev);
 
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between

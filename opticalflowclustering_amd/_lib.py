@@ -109,9 +109,12 @@ _PROTOS = {
     "ofc_stream_create": ([_i, _i, _i, C.POINTER(FbParams), _i, _i, _i, C.POINTER(_vp)], _i),
     "ofc_stream_push_gray": ([_vp, _vp, _ip], _i),
     "ofc_stream_finish": ([_vp, _vp, _i, _ip], _i),
+    "ofc_stream_set_model": ([_vp, _i, _vp, _vp, _i], _i),
+    "ofc_stream_finish_clusters": ([_vp, _vp, _vp, _vp, _i, _ip], _i),
     "ofc_stream_destroy": ([_vp], None),
     "ofc_grid_cell_mean_flow": ([_i, _vp, _i, _i, _i, _i, _vp], _i),
     "ofc_grid_label_counts_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "ofc_grid_assign_counts_dev": ([_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

@@ -556,6 +556,28 @@ int ofc_lloyd_step_dev(int device, const void *X_dev, int dtype, int64_t N, int 
     return OFC_OK;
 }
 
+int ofc_grid_assign_counts_dev(int device, const float *flow_dev, int W, int H, int n_frames, int rows, int cols, int k,
+                               const double *mean, const double *centers_c, int32_t *counts_dev, double *sums_dev)
+{
+    OFC_REQUIRE(flow_dev && centers_c && counts_dev, "null pointer");
+    OFC_REQUIRE(n_frames >= 1 && W >= 1 && H >= 1, "bad size %dx%d x %d frames", W, H, n_frames);
+    OFC_REQUIRE(rows >= 1 && cols >= 1 && W >= cols && H >= rows, "grid %dx%d does not fit %dx%d", rows, cols, W, H);
+    OFC_TRY(check_uv_model(k, mean, centers_c));
+    if ((int64_t)W * H > INT32_MAX) {          // a cell's pixels are numbered in 32 bits
+        set_error("frames of %dx%d pixels are not supported (more than 2^31 - 1)", W, H);
+        return OFC_EUNSUPPORTED;
+    }
+    OFC_TRY(ensure_device(device));
+    const double zero[2] = {0.0, 0.0};
+    StepCtx c;
+    OFC_TRY(c.init(0, 2));
+    OFC_TRY(c.set(mean ? mean : zero, centers_c, k, 2));
+    OFC_TRY(launch_grid_assign_counts(flow_dev, c.state.as<LloydState>(), W, H, n_frames, rows, cols, k, counts_dev, sums_dev,
+                                      nullptr));
+    OFC_HIP(hipStreamSynchronize(nullptr));
+    return OFC_OK;
+}
+
 int ofc_lloyd_inertia_dev(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *mean,
                           const double *centers_c, const uint8_t *labels_dev, double *inertia)
 {

@@ -2,6 +2,8 @@
 #pragma once
 #include "ofc_common.h"
 
+#include <cmath>
+
 namespace ofc {
 
 constexpr int LLOYD_KMAX = 16;   // streaming / batched kernels keep per-lane partials in registers
@@ -78,6 +80,24 @@ constexpr int LLOYD_WINDOW = 16;    // most iterations enqueued per host synchro
 int launch_lloyd_set_centers(LloydState *st, int k, int d, hipStream_t s, int prune_policy = 0);
 int launch_lloyd_inertia(const void *X, int dtype, int64_t N, int d, const LloydState *st,
                          const uint8_t *labels, double *partial, int nblocks, hipStream_t s);
+// grid_labels.hip: the E-step's label of every pixel of flow [n_frames][H][W][2] against st (mean, centres, cn set), counted
+// per grid cell as launch_grid_label_counts counts a label buffer: counts [n_frames][rows*cols][k], sums (or nullptr)
+// [n_frames][rows*cols][k][2]
+int launch_grid_assign_counts(const float *flow, const LloydState *st, int W, int H, int n_frames, int rows, int cols, int k,
+                              int32_t *counts, double *sums, hipStream_t s);
+// OFC_OK, or the refusal of a model both fused entry points share: k outside 1 .. LLOYD_KMAX (OFC_EUNSUPPORTED), a mean
+// (may be nullptr) or a centre that is not finite (OFC_EINVAL)
+inline int check_uv_model(int k, const double *mean, const double *centers_c)
+{
+    OFC_REQUIRE(centers_c, "null pointer");
+    if (k < 1 || k > LLOYD_KMAX) {
+        set_error("k=%d outside the kernel's range (1..%d)", k, LLOYD_KMAX);
+        return OFC_EUNSUPPORTED;
+    }
+    for (int i = 0; i < 2; i++) OFC_REQUIRE(!mean || std::isfinite(mean[i]), "mean[%d] is not finite", i);
+    for (int i = 0; i < 2 * k; i++) OFC_REQUIRE(std::isfinite(centers_c[i]), "centre %d is not finite", i / 2);
+    return OFC_OK;
+}
 int launch_lloyd_farthest(const void *X, int dtype, int64_t N, int d, const LloydState *st,
                           const double *c_old, const uint8_t *labels, const int64_t *excl, int n_excl,
                           double *out, int nblocks, hipStream_t s);

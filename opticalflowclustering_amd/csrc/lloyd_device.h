@@ -1,5 +1,5 @@
-// lloyd_device.h -- device helpers shared by the Lloyd and seeding kernels (lloyd_kernels.hip, lloyd_seed.hip):
-// sample loaders and the deterministic work-group sum.
+// lloyd_device.h -- device helpers shared by the Lloyd and seeding kernels (lloyd_kernels.hip, lloyd_weighted.hip,
+// lloyd_seed.hip) and grid_labels.hip: sample loaders, the E-step's label and the deterministic work-group sum.
 #pragma once
 #include "lloyd_common.h"
 
@@ -61,6 +61,28 @@ __device__ __forceinline__ void load1(const T *X, int64_t i, double (&x)[D])
 {
 #pragma unroll
     for (int f = 0; f < D; f++) x[f] = (double)X[i * D + f];
+}
+
+// the E-step's label of one centred sample: the first strict minimum over j < k of D_j = |c_j|^2 - 2 x.c_j, the dot
+// product as one multiply and a chain of fma.  Every kernel that labels (the Lloyd sweeps, plain and weighted, and
+// grid_labels.hip's fused label-and-count) calls this one function, so they give a sample the same byte.
+template <int D, int KMAX>
+__device__ __forceinline__ int assign_point(const double (&x)[D], const double *c /*[KMAX*D] regs*/,
+                                            const double *cn, int k)
+{
+    double best = 0;
+    int label = 0;
+#pragma unroll
+    for (int j = 0; j < KMAX; j++) {
+        if (j < k) {
+            double acc = x[0] * c[j * D];
+#pragma unroll
+            for (int f = 1; f < D; f++) acc = fma(x[f], c[j * D + f], acc);
+            const double dj = cn[j] - 2.0 * acc;
+            if (j == 0 || dj < best) { best = dj; label = j; }
+        }
+    }
+    return label;
 }
 
 // deterministic work-group sum of NV doubles per thread -> out[NV] (thread 0..NV-1 write)

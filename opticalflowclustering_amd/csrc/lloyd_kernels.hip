@@ -86,27 +86,9 @@ __global__ __launch_bounds__(1024) void k_reduce_records(const double *__restric
 
 // ------------------------------------------------------------------------------------------------
 // E-step (+ M-step accumulation).  Record per work-group: [k*d sums of (x-mean)][k counts][n_changed]
-// (laid out with stride KMAX: sums[j*D+f], counts at KMAX*D + j, changed at KMAX*D + KMAX).
+// (laid out with stride KMAX: sums[j*D+f], counts at KMAX*D + j, changed at KMAX*D + KMAX).  The label is
+// lloyd_device.h's assign_point.
 // ------------------------------------------------------------------------------------------------
-template <int D, int KMAX>
-__device__ __forceinline__ int assign_point(const double (&x)[D], const double *c /*[KMAX*D] regs*/,
-                                            const double *cn, int k)
-{
-    double best = 0;
-    int label = 0;
-#pragma unroll
-    for (int j = 0; j < KMAX; j++) {
-        if (j < k) {
-            double acc = x[0] * c[j * D];
-#pragma unroll
-            for (int f = 1; f < D; f++) acc = fma(x[f], c[j * D + f], acc);
-            const double dj = cn[j] - 2.0 * acc;
-            if (j == 0 || dj < best) { best = dj; label = j; }
-        }
-    }
-    return label;
-}
-
 template <int D>
 __device__ __forceinline__ double sq_euclid_grouped(const double (&a)[D], const double *b)
 {

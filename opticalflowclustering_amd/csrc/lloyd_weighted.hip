@@ -40,26 +40,8 @@ __device__ __forceinline__ void block_reduce_store_w(double (&v)[NV], double *ld
     __syncthreads();
 }
 
-// assign_point_w and sq_euclid_grouped_w repeat lloyd_kernels.hip's assign_point and sq_euclid_grouped word for word: that
-// file and its instantiations stay as they are, and the two translation units share no device code
-template <int D, int KMAX>
-__device__ __forceinline__ int assign_point_w(const double (&x)[D], const double *c, const double *cn, int k)
-{
-    double best = 0;
-    int label = 0;
-#pragma unroll
-    for (int j = 0; j < KMAX; j++) {
-        if (j < k) {
-            double acc = x[0] * c[j * D];
-#pragma unroll
-            for (int f = 1; f < D; f++) acc = fma(x[f], c[j * D + f], acc);
-            const double dj = cn[j] - 2.0 * acc;
-            if (j == 0 || dj < best) { best = dj; label = j; }
-        }
-    }
-    return label;
-}
-
+// the label is lloyd_device.h's assign_point.  sq_euclid_grouped_w repeats lloyd_kernels.hip's sq_euclid_grouped word for
+// word: that file and its instantiations stay as they are
 template <int D>
 __device__ __forceinline__ double sq_euclid_grouped_w(const double (&a)[D], const double *b)
 {
@@ -146,7 +128,7 @@ __global__ __launch_bounds__((LloydWLanes<D, KMAX>::value)) void k_lloyd_assign_
         for (int p = 0; p < 4; p++) {
 #pragma unroll
             for (int f = 0; f < D; f++) x[p][f] -= m[f];
-            nl[p] = assign_point_w<D, KMAX>(x[p], c, cn, k);
+            nl[p] = assign_point<D, KMAX>(x[p], c, cn, k);
         }
         if (ACCUM) {
 #pragma unroll
@@ -211,7 +193,7 @@ __global__ __launch_bounds__((LloydWLanes<D, KMAX>::value)) void k_lloyd_assign_
         const double w = (double)W[i];
 #pragma unroll
         for (int f = 0; f < D; f++) x[f] -= m[f];
-        const int l = assign_point_w<D, KMAX>(x, c, cn, k);
+        const int l = assign_point<D, KMAX>(x, c, cn, k);
         if (ACCUM) {
             accumulate(l, x, w);
             if (MODE == 1) changed += (l != labels[i]);

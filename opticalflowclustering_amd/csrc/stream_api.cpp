@@ -1,7 +1,10 @@
 // stream_api.cpp -- C ABI of libofc.so, part 4: streaming ingest with double-buffered pinned uploads
 // (BASELINE.json configs[4] shape).  Two slots; while slot A's batch computes on the engine's stream, the host fills
 // slot B's pinned buffer and its hipMemcpyAsync runs on the copy stream.  Consecutive batches overlap by one frame.
+// With a model (ofc_stream_set_model) every batch's field is also labelled against it and counted per cell, behind the
+// cell means on the compute stream, while the field is still where the flow left it.
 #include "color_common.h"
+#include "lloyd_common.h"
 
 #include <memory>
 
@@ -23,6 +26,12 @@ struct ofc_stream {
     DevBuf cells;                      // [max_pairs][rows*cols][2] f32, grows
     size_t cells_cap = 0;              // pairs
     int pairs_submitted = 0;
+    // the model, when there is one (k > 0): its LloydState on the device, and what it says about every pair so far
+    int k = 0;
+    bool with_sums = false;
+    DevBuf model;                      // LloydState
+    DevBuf counts, sums;               // [max_pairs][rows*cols][k] int32, [...][k][2] f64 (with_sums): grow with `cells`
+    size_t clusters_cap = 0;           // pairs
 };
 
 namespace {
@@ -44,19 +53,48 @@ int ensure_cells(ofc_stream *s, int need_pairs)
     return OFC_OK;
 }
 
-// submit the frames packed in slot `i` (n >= 2): async upload, flow, cell means
+// room for the counts (and sums) of need_pairs pairs: same growth as ensure_cells, what was counted so far is kept
+int ensure_clusters(ofc_stream *s, int need_pairs)
+{
+    if ((size_t)need_pairs <= s->clusters_cap) return OFC_OK;
+    const size_t cap = std::max<size_t>(need_pairs, s->clusters_cap ? s->clusters_cap * 2 : 256);
+    const size_t per = sizeof(int32_t) * s->rows * s->cols * s->k;
+    DevBuf nc, ns;
+    OFC_TRY(nc.alloc(cap * per));
+    if (s->with_sums) OFC_TRY(ns.alloc(cap * per * 4));
+    if (s->counts.p && s->pairs_submitted) {
+        OFC_HIP(hipStreamSynchronize(s->compute));
+        OFC_HIP(hipMemcpy(nc.p, s->counts.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
+        if (s->with_sums) OFC_HIP(hipMemcpy(ns.p, s->sums.p, (size_t)s->pairs_submitted * per * 4, hipMemcpyDeviceToDevice));
+    }
+    std::swap(s->counts.p, nc.p);
+    std::swap(s->counts.bytes, nc.bytes);
+    std::swap(s->sums.p, ns.p);
+    std::swap(s->sums.bytes, ns.bytes);
+    s->clusters_cap = cap;
+    return OFC_OK;
+}
+
+// submit the frames packed in slot `i` (n >= 2): async upload, flow, cell means, and with a model the cluster counts
 int submit(ofc_stream *s, int i)
 {
     ofc_stream::Slot &sl = s->slot[i];
     const int npair = sl.n_frames - 1;
     const size_t P = (size_t)s->W * s->H;
     OFC_TRY(ensure_cells(s, s->pairs_submitted + npair));
+    if (s->k) OFC_TRY(ensure_clusters(s, s->pairs_submitted + npair));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
     OFC_TRY(ofc_flow_calc_frames_dev(s->flow, sl.frames.as<uint8_t>(), sl.n_frames, sl.flows.as<float>()));
     float *dst = s->cells.as<float>() + (size_t)s->pairs_submitted * 2 * s->rows * s->cols;
     OFC_TRY(launch_grid_cell_mean_flow(sl.flows.as<float>(), s->W, s->H, npair, s->rows, s->cols, dst, s->compute));
+    if (s->k) {
+        const size_t at = (size_t)s->pairs_submitted * s->rows * s->cols * s->k;
+        OFC_TRY(launch_grid_assign_counts(sl.flows.as<float>(), s->model.as<LloydState>(), s->W, s->H, npair, s->rows, s->cols,
+                                          s->k, s->counts.as<int32_t>() + at,
+                                          s->with_sums ? s->sums.as<double>() + at * 2 : nullptr, s->compute));
+    }
     OFC_HIP(hipEventRecord(sl.done, s->compute));
     sl.busy = true;
     sl.inflight_pairs = npair;
@@ -128,10 +166,9 @@ int ofc_stream_push_gray(ofc_stream_t *s, const uint8_t *gray, int *pairs_done)
     return OFC_OK;
 }
 
-int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pairs)
+// flush the partial batch and wait for everything submitted
+static int flush(ofc_stream *s)
 {
-    OFC_REQUIRE(s && n_pairs, "null pointer");
-    OFC_TRY(ensure_device(s->device));
     ofc_stream::Slot &sl = s->slot[s->cur];
     if (sl.n_frames >= 2) {
         if (sl.busy) { OFC_HIP(hipEventSynchronize(sl.done)); sl.busy = false; }
@@ -141,11 +178,67 @@ int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pai
     OFC_HIP(hipStreamSynchronize(s->copy));
     OFC_HIP(hipStreamSynchronize(s->compute));
     for (auto &q : s->slot) q.busy = false;
+    return OFC_OK;
+}
+
+int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pairs)
+{
+    OFC_REQUIRE(s && n_pairs, "null pointer");
+    OFC_TRY(ensure_device(s->device));
+    OFC_TRY(flush(s));
     *n_pairs = s->pairs_submitted;
     if (cell_uv) {
         OFC_REQUIRE(max_pairs >= s->pairs_submitted, "cell_uv holds %d pairs, %d produced", max_pairs, s->pairs_submitted);
         OFC_HIP(hipMemcpy(cell_uv, s->cells.p, sizeof(float) * 2 * s->rows * s->cols * (size_t)s->pairs_submitted,
                           hipMemcpyDeviceToHost));
+    }
+    s->pairs_submitted = 0;
+    return OFC_OK;
+}
+
+int ofc_stream_set_model(ofc_stream_t *s, int k, const double *mean, const double *centers_c, int with_sums)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (k != 0) OFC_TRY(check_uv_model(k, mean, centers_c));
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: set the model on a fresh stream or straight after a finish");
+    OFC_TRY(ensure_device(s->device));
+    if (k != 0) {
+        LloydState st;
+        memset(&st, 0, sizeof(st));
+        if (mean) memcpy(st.mean, mean, sizeof(double) * 2);
+        memcpy(st.centers, centers_c, sizeof(double) * 2 * k);
+        if (!s->model.p) OFC_TRY(s->model.alloc(sizeof(LloydState)));
+        // nothing of this stream is in flight (checked above): the state is free to be rewritten
+        OFC_HIP(hipMemcpyAsync(s->model.p, &st, sizeof(st), hipMemcpyHostToDevice, s->compute));
+        OFC_TRY(launch_lloyd_set_centers(s->model.as<LloydState>(), k, 2, s->compute));
+        OFC_HIP(hipStreamSynchronize(s->compute));
+    }
+    if (k != s->k || (with_sums != 0) != s->with_sums) {       // the buffers' layout changes: they are empty, start over
+        s->counts.release();
+        s->sums.release();
+        s->clusters_cap = 0;
+    }
+    s->k = k;
+    s->with_sums = k != 0 && with_sums != 0;
+    return OFC_OK;
+}
+
+int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts, double *sums, int max_pairs, int *n_pairs)
+{
+    OFC_REQUIRE(s && n_pairs, "null pointer");
+    OFC_REQUIRE(s->k > 0, "the stream has no model (ofc_stream_set_model)");
+    OFC_REQUIRE(!sums || s->with_sums, "the model was set without sums");
+    OFC_TRY(ensure_device(s->device));
+    OFC_TRY(flush(s));
+    const size_t n = (size_t)s->pairs_submitted, cells = (size_t)s->rows * s->cols;
+    *n_pairs = s->pairs_submitted;
+    if (cell_uv || counts || sums)
+        OFC_REQUIRE(max_pairs >= s->pairs_submitted, "the outputs hold %d pairs, %d produced", max_pairs, s->pairs_submitted);
+    if (n) {
+        if (cell_uv) OFC_HIP(hipMemcpy(cell_uv, s->cells.p, sizeof(float) * 2 * cells * n, hipMemcpyDeviceToHost));
+        if (counts) OFC_HIP(hipMemcpy(counts, s->counts.p, sizeof(int32_t) * cells * s->k * n, hipMemcpyDeviceToHost));
+        if (sums) OFC_HIP(hipMemcpy(sums, s->sums.p, sizeof(double) * 2 * cells * s->k * n, hipMemcpyDeviceToHost));
     }
     s->pairs_submitted = 0;
     return OFC_OK;

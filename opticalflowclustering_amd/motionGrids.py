@@ -8,6 +8,13 @@ gives that cluster's direction (computeOpticalFlowModule.py:25-33: hue = angle /
 
     python -m opticalflowclustering_amd.motionGrids --path CLIP -c 5 -f OUT.csv --save-model centres.npy
     python -m opticalflowclustering_amd.motionGrids --path OTHER -c 5 -f OTHER.csv --model centres.npy
+    python -m opticalflowclustering_amd.motionGrids --path LONG -c 5 -f LONG.csv --model centres.npy --stream
+
+With --stream the clip is never resident: its frames are read one at a time and pushed through a FlowStream that carries
+the model, which labels and counts every batch's field on the device while it is there (FlowStream.finish_clusters), so
+the clip may be longer than memory.  A stream has no field mean before it ends: it labels against mean (0, 0), as
+KMeans.predict does, where ClipPipeline.assign centres the arithmetic by the field's mean.  The two agree except where a
+pixel's two nearest centres tie to the rounding of the expanded form; bit equality of the two routes is not promised.
 """
 import argparse
 import os
@@ -81,7 +88,15 @@ def parse_arguments(argv=None):
     ap.add_argument("--value", choices=("hue", "label"), default="hue",
                     help="a cell's value: the hue of its dominant cluster's direction, or that cluster's index")
     ap.add_argument("--device", type=int, default=0)
-    return ap.parse_args(argv)
+    ap.add_argument("--stream", action="store_true",
+                    help="with --model: read the clip frame by frame and count on a FlowStream; the clip is never resident")
+    ap.add_argument("--batch-pairs", type=int, default=8, help="frame pairs per batch of the --stream route")
+    args = ap.parse_args(argv)
+    if args.stream and not args.model:
+        ap.error("--stream applies a model to arriving frames and cannot fit one: it requires --model")
+    if args.batch_pairs < 1:
+        ap.error("--batch-pairs must be at least 1")
+    return args
 
 
 def _load_centres(path, k, what):
@@ -91,29 +106,57 @@ def _load_centres(path, k, what):
     return cen
 
 
-def read_gray_frames(path, device=0):
-    """every frame of the clip as (T, H, W) u8 grey (cv2's BGR2GRAY, on the device, for three-channel frames)"""
+def gray_frames(path, device=0):
+    """the clip's frames one at a time as (H, W) u8 grey (cv2's BGR2GRAY, on the device, for three-channel frames)"""
     from .frameio import FrameSource
     from .vis import bgr2gray
     cap = FrameSource(path)
-    frames = []
-    while cap.isOpened():
-        ret, frame = cap.read()
-        if not ret:
-            break
-        frames.append(bgr2gray(frame, device) if frame.ndim == 3 else np.ascontiguousarray(frame, np.uint8))
-    cap.release()
+    try:
+        while cap.isOpened():
+            ret, frame = cap.read()
+            if not ret:
+                break
+            yield bgr2gray(frame, device) if frame.ndim == 3 else np.ascontiguousarray(frame, np.uint8)
+    finally:
+        cap.release()
+
+
+def read_gray_frames(path, device=0):
+    """every frame of the clip as (T, H, W) u8 grey (cv2's BGR2GRAY, on the device, for three-channel frames)"""
+    frames = list(gray_frames(path, device))
     if len(frames) < 2:
         raise RuntimeError(f"{path!r} has {len(frames)} frame(s); a flow field needs two")
     return np.stack(frames)
 
 
+def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0):
+    """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident"""
+    from .stream import FlowStream
+    fs, n = None, 0
+    try:
+        for gray in gray_frames(path, device):
+            if fs is None:
+                fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, centers=centers)
+            fs.push(gray)
+            n += 1
+        if n < 2:
+            raise RuntimeError(f"{path!r} has {n} frame(s); a flow field needs two")
+        return fs.finish_clusters()[1]
+    finally:
+        if fs is not None:
+            fs.close()
+
+
 def main(argv=None):
     args = parse_arguments(argv)
-    from .pipeline import ClipPipeline
     k = args.clusters
     given = _load_centres(args.model, k, "--model") if args.model else \
         _load_centres(args.init, k, "--init") if args.init != "k-means++" else None
+    if args.stream:
+        centers = given
+        counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device)
+        return _write_outputs(args, counts, centers)
+    from .pipeline import ClipPipeline
     frames = read_gray_frames(args.path, args.device)
     T, H, W = frames.shape
     pipe = ClipPipeline(W, H, T, device=args.device)
@@ -133,6 +176,10 @@ def main(argv=None):
         counts = pipe.cell_clusters(args.rows, args.cols)
     finally:
         pipe.close()
+    return _write_outputs(args, counts, centers)
+
+
+def _write_outputs(args, counts, centers):
     write_csv(args.csv, hue_rows(counts, centers) if args.value == "hue" else dominant(counts))
     if args.save_model:
         np.save(args.save_model, centers)

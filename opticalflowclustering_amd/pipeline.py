@@ -151,11 +151,8 @@ class ClipPipeline:
         self._label_k = len(fit[0])
         return fit
 
-    def assign(self, centers):
-        """label the resident (u,v) vectors against the given (k,2) centres without fitting (a model fitted on another
-        clip, say): one E-step (ofc_lloyd_step_dev, nothing accumulated), centred by this field's own column mean as the
-        fit's final E-step is.  The labels replace the resident ones; cell_clusters() summarises them.  Under a
-        communicator this is rank-local: this rank's pairs, this rank's mean, no collective."""
+    def _centred_model(self, centers):
+        """-> (k, the resident field's column mean (2,), centres minus that mean (k,2)): what assign labels against"""
         self.sync()
         cen = np.ascontiguousarray(centers, np.float64)
         if cen.ndim != 2 or cen.shape[1] != 2 or len(cen) < 1:
@@ -167,29 +164,51 @@ class ClipPipeline:
             check(load().ofc_lloyd_colstats_dev(self.device, C.c_void_p(self.flows.ptr), _lib.F32, N, 2, None, 0,
                                                 _lib.ptr(colsum)))
         mean = np.ascontiguousarray(colsum / N)
-        self._label_k = None
-        check(load().ofc_lloyd_step_dev(self.device, C.c_void_p(self.flows.ptr), _lib.F32, N, 2, len(cen), _lib.ptr(mean),
-                                        _lib.ptr(np.ascontiguousarray(cen - mean)), C.c_void_p(self.labels.ptr), 0, None))
-        self._label_k = len(cen)
+        return len(cen), mean, np.ascontiguousarray(cen - mean)
 
-    def cell_clusters(self, rows=14, cols=25, sums=False):
+    def assign(self, centers):
+        """label the resident (u,v) vectors against the given (k,2) centres without fitting (a model fitted on another
+        clip, say): one E-step (ofc_lloyd_step_dev, nothing accumulated), centred by this field's own column mean as the
+        fit's final E-step is.  The labels replace the resident ones; cell_clusters() summarises them.  Under a
+        communicator this is rank-local: this rank's pairs, this rank's mean, no collective."""
+        k, mean, cen_c = self._centred_model(centers)
+        N = self.n_pairs * self.W * self.H
+        self._label_k = None
+        check(load().ofc_lloyd_step_dev(self.device, C.c_void_p(self.flows.ptr), _lib.F32, N, 2, k, _lib.ptr(mean),
+                                        _lib.ptr(cen_c), C.c_void_p(self.labels.ptr), 0, None))
+        self._label_k = k
+
+    def cell_clusters(self, rows=14, cols=25, sums=False, centers=None):
         """what the resident labels say per grid cell (ofc_grid_label_counts_dev, the grid of KmeanGrids.py:56-59):
         counts (n_pairs, rows*cols, k) int32 = pixels of the cell in each cluster, and with sums=True also
         (n_pairs, rows*cols, k, 2) f64 = the sums of their (u, v); only these few numbers leave the device.
         Needs labels: after run_kmeans() or assign(), not after a run_flow() that replaced the field.
+        With centers= ((k,2), a model fitted elsewhere) the result is that of assign(centers) followed by
+        cell_clusters(rows, cols, sums), from one sweep of the field (ofc_grid_assign_counts_dev): every vector is
+        labelled as assign labels it, centred by this field's own mean, and counted at once.  The resident labels are
+        neither needed nor touched, and stay those of the last run_kmeans() / assign().
         Under a communicator the result covers this rank's pairs; the ranks' rows concatenated in rank order are the
         single-rank result (a pair's rows depend on that pair alone), so no collective is involved."""
-        if self._label_k is None:
+        if centers is not None:
+            k, mean, cen_c = self._centred_model(centers)
+        elif self._label_k is None:
             raise ValueError("cell_clusters needs labels for the resident field: call run_kmeans() or assign() first "
                              "(run_flow() discards them)")
-        k, n = self._label_k, self.n_pairs
+        else:
+            k = self._label_k
+        n = self.n_pairs
         nout = max(n * int(rows) * int(cols) * k, 1)      # the library refuses a grid that does not fit
         cnt = DeviceBuffer(nout * 4, self.device)
         sm = DeviceBuffer(nout * 16, self.device) if sums else None
         try:
-            check(load().ofc_grid_label_counts_dev(self.device, C.c_void_p(self.labels.ptr),
-                                                   C.c_void_p(self.flows.ptr) if sums else None, self.W, self.H, n, rows, cols,
-                                                   k, C.c_void_p(cnt.ptr), C.c_void_p(sm.ptr) if sums else None))
+            if centers is not None:
+                check(load().ofc_grid_assign_counts_dev(self.device, C.c_void_p(self.flows.ptr), self.W, self.H, n, rows,
+                                                        cols, k, _lib.ptr(mean), _lib.ptr(cen_c), C.c_void_p(cnt.ptr),
+                                                        C.c_void_p(sm.ptr) if sums else None))
+            else:
+                check(load().ofc_grid_label_counts_dev(self.device, C.c_void_p(self.labels.ptr),
+                                                       C.c_void_p(self.flows.ptr) if sums else None, self.W, self.H, n, rows,
+                                                       cols, k, C.c_void_p(cnt.ptr), C.c_void_p(sm.ptr) if sums else None))
             counts = cnt.download((n, rows * cols, k), np.int32)
             return (counts, sm.download((n, rows * cols, k, 2), np.float64)) if sums else counts
         finally:

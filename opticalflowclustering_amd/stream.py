@@ -1,7 +1,9 @@
 """Streaming ingest (BASELINE.json configs[4] shape): frames are pushed one at a time (as a decoder produces them),
 packed into pinned ring buffers, uploaded with hipMemcpyAsync on a copy stream while the previous batch computes,
 and reduced to the grid-cell averaged flow (rows*cols (u,v) means per pair).  k-means over those vectors is then a
-small streaming-Lloyd problem (cluster.KMeans)."""
+small streaming-Lloyd problem (cluster.KMeans).  With a model (fitted (k,2) centres) the stream also applies it: every
+pair's field is labelled against the centres and counted per grid cell on the device while it is still there
+(finish_clusters), so a fit can be deployed on footage that keeps arriving or is longer than memory."""
 import ctypes as C
 
 import numpy as np
@@ -10,13 +12,33 @@ from ._lib import FbParams, check, load, ptr
 
 
 class FlowStream:
-    def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0):
+    def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
         check(load().ofc_stream_create(device, W, H, C.byref(self.params), batch_pairs, rows, cols, C.byref(h)))
         self._h = h
         self.pushed = 0
+        self.k, self.sums = 0, False
+        if centers is not None:
+            self.set_model(centers, mean, sums)
+
+    def set_model(self, centers, mean=None, sums=False):
+        """from the next batch on, label every pair's field against `centers` ((k,2), un-centred; None removes the model)
+        and count it per cell (ofc_stream_set_model, the kernel of vis.grid_assign_counts).  Only on a stream that holds
+        no frame and no undelivered result: fresh, or straight after finish() / finish_clusters(); ValueError otherwise,
+        and the model stays as it was.
+        mean=None labels against mean (0, 0), KMeans.predict's un-centred E-step: a stream has no field mean before the
+        clip ends.  ClipPipeline.assign centres by the field's mean; the two agree except where a pixel's two nearest
+        centres tie to the rounding of the expanded form, so no bit equality between the two routes is promised."""
+        if centers is None:
+            check(load().ofc_stream_set_model(self._h, 0, None, None, 0))
+            self.k, self.sums = 0, False
+            return
+        from .vis import _model_args
+        k, mean, cen_c = _model_args(centers, mean)
+        check(load().ofc_stream_set_model(self._h, k, ptr(mean), ptr(cen_c), int(bool(sums))))
+        self.k, self.sums = k, bool(sums)
 
     def push(self, gray):
         gray = np.ascontiguousarray(gray, np.uint8)
@@ -35,6 +57,20 @@ class FlowStream:
         check(load().ofc_stream_finish(self._h, ptr(out), max(n, 1), C.byref(got)))
         self.pushed = 0
         return out[:got.value]
+
+    def finish_clusters(self):
+        """finish() that also delivers what the model says: -> (cell_uv, counts (n_pairs, rows*cols, k) int32), and with
+        a model set with sums=True also sums (n_pairs, rows*cols, k, 2) f64.  ValueError without a model."""
+        n = max(self.pushed - 1, 0)
+        cells, k = self.rows * self.cols, max(self.k, 1)
+        out = np.empty((max(n, 1), cells, 2), np.float32)
+        counts = np.empty((max(n, 1), cells, k), np.int32)
+        sums = np.empty((max(n, 1), cells, k, 2), np.float64) if self.sums else None
+        got = C.c_int()
+        check(load().ofc_stream_finish_clusters(self._h, ptr(out), ptr(counts), ptr(sums), max(n, 1), C.byref(got)))
+        self.pushed = 0
+        res = (out[:got.value], counts[:got.value])
+        return res + (sums[:got.value],) if self.sums else res
 
     def close(self):
         if getattr(self, "_h", None):

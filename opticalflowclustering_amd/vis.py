@@ -97,6 +97,47 @@ def grid_label_counts(labels, k, rows=14, cols=25, flow=None, device=0):
             b.free()
 
 
+def _model_args(centers, mean):
+    """(k, mean (2,) f64, centred centres (k,2) f64) as ofc_lloyd_step_dev and the fused grid kernel take a model"""
+    cen = np.ascontiguousarray(centers, np.float64)
+    if cen.ndim != 2 or cen.shape[1] != 2 or len(cen) < 1:
+        raise ValueError(f"centers should be a (k,2) array, got shape {cen.shape}")
+    mean = np.zeros(2) if mean is None else np.ascontiguousarray(mean, np.float64)
+    if mean.shape != (2,):
+        raise ValueError(f"mean should be 2 values, got shape {mean.shape}")
+    return len(cen), mean, np.ascontiguousarray(cen - mean)
+
+
+def grid_assign_counts(flow, centers, rows=14, cols=25, mean=None, sums=False, device=0):
+    """grid_label_counts of the labels a model gives the field, in one sweep and without the labels
+    (ofc_grid_assign_counts_dev): every (u, v) gets the label ofc_lloyd_step_dev's E-step gives it against `centers`
+    ((k,2), un-centred) with the arithmetic centred by `mean` (None = (0, 0): KMeans.predict's un-centred E-step;
+    ClipPipeline.assign centres by the field's own mean, and the two agree except where a pixel's two nearest centres
+    tie to the rounding of the expanded form |c|^2 - 2 x.c), and is counted in its grid cell.
+    flow (n, H, W, 2) or (H, W, 2) f32 -> counts (n, rows*cols, k) int32, or with sums=True (counts, sums
+    (n, rows*cols, k, 2) f64 of the (u, v) counted)"""
+    flow = np.ascontiguousarray(flow, np.float32)
+    if flow.ndim == 3:
+        flow = flow[None]
+    if flow.ndim != 4 or flow.shape[3] != 2:
+        raise ValueError(f"flow must be (n, H, W, 2) or (H, W, 2), got shape {flow.shape}")
+    n, H, W = flow.shape[:3]
+    k, mean, cen_c = _model_args(centers, mean)
+    rows, cols = int(rows), int(cols)
+    nout = max(n * rows * cols * k, 1)                # the library refuses a bad k / rows / cols; nothing is read back then
+    bufs = [DeviceBuffer(max(flow.nbytes, 1), device).upload(flow), DeviceBuffer(nout * 4, device)]
+    try:
+        if sums:
+            bufs.append(DeviceBuffer(nout * 16, device))
+        check(load().ofc_grid_assign_counts_dev(device, bufs[0].ptr, W, H, n, rows, cols, k, ptr(mean), ptr(cen_c),
+                                                bufs[1].ptr, bufs[2].ptr if sums else None))
+        counts = bufs[1].download((n, rows * cols, k), np.int32)
+        return (counts, bufs[2].download((n, rows * cols, k, 2), np.float64)) if sums else counts
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def kmeans_fit_batched(X, offsets, k, init=None, max_iter=300, tol=1e-4, device=0):
     """many independent u8 RGBA problems in one launch.
     -> centers (P,k,4) f64, counts (P,k) = bincount(predict), labels (total,), n_iter (P,)"""
