@@ -151,9 +151,18 @@ int ofc_flow_resize(int device, const float *flow, int sw, int sh, int dw, int d
  * oracle/farneback_ref.c, the loop of FarnebackUpdateFlow_Blur) from flow_in, with the engine's fused kernels.
  * mode 0: one launch per iteration (k_flow_iter); mode 1: two iterations per launch where possible (k_flow_iter2);
  * mode 2: one launch per iteration with the 3-waves-per-SIMD kernel (k_flow_iter_w3); rows_per_block 0 = automatic
- * strip height.  Parity-test hook. */
+ * strip height.  Every mode honours rows_per_block: mode 0, the kernel the engine runs, rounds it up to a multiple of 16
+ * (a value above H is one strip) and refuses a negative one with OFC_EINVAL; modes 1 and 2 round up to a multiple of 2.
+ * The result does not depend on the height.  Parity-test hook. */
 int ofc_flow_iterate(int device, const float *R0, const float *R1, const float *flow_in, int W, int H,
                      int winsize, int iters, int mode, int rows_per_block, float *flow_out);
+/* The strip heights the launches' cost models pick for a W x H pyramid level in a batch of n_pairs pairs (n_pairs + 1
+ * images): out[0] rows per work-group of the fused iteration (k_flow_iter; 0 for winsize > 15, which runs staged), out[1]
+ * of the staged box mean + solve (k_box_solve; the fixed height of k_box_solve_wide from winsize 19 on), out[2] of the
+ * polynomial expansion over the n_pairs + 1 images.  Host only: no device is touched.  OFC_EINVAL: null pointer, W or H
+ * or n_pairs < 1, winsize even or outside 5 .. OFC_WINSIZE_MAX.  Test hook: the suite's case tables are checked against
+ * these models themselves. */
+int ofc_flow_launch_geometry(int W, int H, int n_pairs, int winsize, int out[3]);
 /* bench hook: one 1080p-style level of `n_pairs` resident pairs, the last two of the three iterations of a level
  * timed with HIP events on their stream: mode 0 = two single-iteration launches, mode 1 = one two-iteration launch,
  * mode 2 = two launches of the 3-waves-per-SIMD kernel.

@@ -65,6 +65,7 @@ _PROTOS = {
     "ofc_box_solve": ([_i, _vp, _i, _i, _i, _vp], _i),
     "ofc_flow_resize": ([_i, _vp, _i, _i, _i, _i, _f, _vp], _i),
     "ofc_flow_iterate": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "ofc_flow_launch_geometry": ([_i, _i, _i, _i, _ip], _i),
     "ofc_bench_flow_iters": ([_i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_bench_polyexp": ([_i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_bgr2gray": ([_i, _vp, _i, _i, _vp], _i),

@@ -1473,6 +1473,8 @@ int flow_iter_rows(int W, int H, int npair, int winsize)
 {
     // cost model: a launch runs in ceil(blocks / resident) rounds (224 VGPRs -> 2 work-groups per CU), each as
     // long as one strip incl. its 2m-row window warm-up.  Pick the strip count that minimises rounds x strip.
+    // (Speed only: every height gives the same bits.  tests/test_flow_geometry_host.py asks this model, through
+    // ofc_flow_launch_geometry, which heights the suite's tables reach -- retune it and that test says what went missing.)
     const int tiles_x = cdiv(W, 256 - (winsize - 1));
     const int resident = 2 * 256;
     int best_rows = cdiv(H, 16) * 16;
@@ -1503,10 +1505,14 @@ static int flow_iter_check(int W, int H, int winsize)
 
 int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out,
                      int npair, int W, int H, int winsize, hipStream_t s, const float *coarse, int sw, int sh,
-                     float mul, double *uv_sum, double *uv_scratch, size_t uv_scratch_doubles)
+                     float mul, double *uv_sum, double *uv_scratch, size_t uv_scratch_doubles, int rows_per_block)
 {
     OFC_TRY(flow_iter_check(W, H, winsize));
-    const int rows_per_block = flow_iter_rows(W, H, npair, winsize);
+    if (rows_per_block < 0) { set_error("rows_per_block %d is negative (0 = automatic)", rows_per_block); return OFC_EINVAL; }
+    // a height of the caller's (the parity tests walk every strip height on small frames) is rounded up to whole
+    // super-steps, as the kernel needs; one above the frame is one strip
+    if (rows_per_block == 0) rows_per_block = flow_iter_rows(W, H, npair, winsize);
+    else rows_per_block = cdiv(std::min(rows_per_block, 1 << 30), 16) * 16;
     UpsArgs u;
     u.src = coarse; u.sw = sw; u.sh = sh; u.mul = mul;
     u.scx = coarse ? (double)sw / W : 1.0; u.scy = coarse ? (double)sh / H : 1.0;

@@ -732,11 +732,23 @@ int ofc_flow_iterate(int device, const float *R0, const float *R1, const float *
         const int n = (mode == 1 && iters - i >= 2) ? 2 : 1;
         if (n == 2) OFC_TRY(launch_flow_iter2(dR.as<float>(), 5 * P, cur, nxt, 1, W, H, winsize, nullptr, rows_per_block));
         else if (mode == 2) OFC_TRY(launch_flow_iter_w3(dR.as<float>(), 5 * P, cur, nxt, 1, W, H, winsize, nullptr, rows_per_block));
-        else OFC_TRY(launch_flow_iter(dR.as<float>(), 5 * P, cur, nxt, 1, W, H, winsize, nullptr));
+        else OFC_TRY(launch_flow_iter(dR.as<float>(), 5 * P, cur, nxt, 1, W, H, winsize, nullptr, nullptr, 0, 0, 1.f, nullptr, nullptr, 0,
+                                      rows_per_block));
         std::swap(cur, nxt);
         i += n;
     }
     OFC_HIP(hipMemcpy(flow_out, cur, sizeof(float) * 2 * P, hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+int ofc_flow_launch_geometry(int W, int H, int n_pairs, int winsize, int out[3])
+{
+    OFC_REQUIRE(out, "null pointer");
+    OFC_REQUIRE(W >= 1 && H >= 1 && n_pairs >= 1, "bad size / pair count");
+    OFC_REQUIRE(winsize >= 5 && winsize <= OFC_WINSIZE_MAX && (winsize & 1), "winsize must be odd, 5 .. OFC_WINSIZE_MAX");
+    out[0] = winsize <= 15 ? flow_iter_rows(W, H, n_pairs, winsize) : 0;
+    out[1] = winsize >= WINSIZE_WIDE_MIN ? box_wide_rows(winsize) : box_default_rows(W, H, n_pairs);
+    out[2] = polyexp_default_rows(W, H, n_pairs + 1);
     return OFC_OK;
 }
 

@@ -59,13 +59,22 @@ def flow_resize(flow, dw, dh, mul=1.0, device=0):
 
 
 def flow_iterate(R0, R1, flow_in, iters, winsize=15, mode=0, rows_per_block=0, device=0):
-    """`iters` Farneback iterations from flow_in with the engine's fused kernels (mode 1: two iterations per launch)"""
+    """`iters` Farneback iterations from flow_in with the engine's fused kernels (mode 1: two iterations per launch);
+    rows_per_block: strip height of every mode, 0 = the cost model's (mode 0 rounds up to a multiple of 16)"""
     R0, R1, flow_in = (np.ascontiguousarray(a, np.float32) for a in (R0, R1, flow_in))
     H, W = flow_in.shape[:2]
     out = np.empty((H, W, 2), np.float32)
     check(load().ofc_flow_iterate(device, ptr(R0), ptr(R1), ptr(flow_in), W, H, winsize, iters, mode, rows_per_block,
                                   ptr(out)))
     return out
+
+
+def flow_launch_geometry(W, H, n_pairs, winsize=15):
+    """(rows of k_flow_iter, rows of k_box_solve, rows of k_polyexp over n_pairs + 1 images) the cost models pick for a
+    W x H level (ofc_flow_launch_geometry); needs no device"""
+    out = (C.c_int * 3)()
+    check(load().ofc_flow_launch_geometry(W, H, n_pairs, winsize, out))
+    return tuple(out)
 
 
 def bench_flow_iters(W, H, n_pairs, reps, mode, device=0):
