@@ -440,6 +440,19 @@ int ofc_stream_set_model(ofc_stream_t *s, int k, const double *mean, const doubl
  * OFC_EINVAL without a model, or with sums != NULL on a model without sums.
  * ofc_stream_finish on a stream with a model returns the cell means as ever and drops the counts. */
 int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts, double *sums, int max_pairs, int *n_pairs);
+/* A stream that also builds the (u,v) histogram of its footage (see "Histogram of flow vectors" below): from the next
+ * batch on, every pair's field is added to the stream's table (ofc_uv_hist_accum_dev's kernel, on the compute stream behind
+ * the cell means and the model's counts of the same batch, so *pairs_done keeps its meaning).  The table starts at zero.
+ * bins, range as for ofc_uv_hist_accum_dev (anything else: OFC_EINVAL); bins = 0 removes the table: the stream then
+ * launches exactly what a stream that never had one launches.
+ * Same precondition as ofc_stream_set_model: no frame and no undelivered result, otherwise OFC_EINVAL and nothing changes.
+ * Setting the bins and range the stream already has keeps the table and what is in it; any other pair starts a new one. */
+int ofc_stream_set_histogram(ofc_stream_t *s, int bins, float range);
+/* Copy the stream's table out (table_host: 3*bins*bins + 1 int64, may be NULL) and zero it when reset != 0.  Legal under
+ * ofc_stream_set_histogram's precondition only, i.e. straight after a finish (or on a fresh stream: all zeros); OFC_EINVAL
+ * otherwise, and without a histogram.  A finish neither delivers nor clears the table: it spans finishes until it is reset,
+ * so one fit can cover several clips. */
+int ofc_stream_read_histogram(ofc_stream_t *s, int64_t *table_host, int reset);
 void ofc_stream_destroy(ofc_stream_t *s);
 /* per-cell mean of a flow field (host buffers): flow HxWx2 f32 -> cell_uv rows*cols x 2 f32 */
 int ofc_grid_cell_mean_flow(int device, const float *flow, int W, int H, int rows, int cols, float *cell_uv);
@@ -469,6 +482,33 @@ int ofc_grid_label_counts_dev(int device, const uint8_t *labels_dev, const float
  * OFC_EUNSUPPORTED: k outside 1 .. 16; W*H above 2^31 - 1.  Everything is checked before anything is launched. */
 int ofc_grid_assign_counts_dev(int device, const float *flow_dev, int W, int H, int n_frames, int rows, int cols, int k,
                                const double *mean, const double *centers_c, int32_t *counts_dev, double *sums_dev);
+
+/* ------------------------------------------------------------------------------------------
+ * Histogram of flow vectors: per bin of the (u,v) plane an exact count and exact fixed-point sums of its members.  A
+ * weighted Lloyd fit over the bin means (ofc_kmeans_fit_w: points = sum / count / 65536, weights = counts) stands in for
+ * the fit over the field, whose vectors need not be resident (opticalflowclustering_amd/uvhist.py).  No reference
+ * counterpart.
+ * bins = B: a power of two, 16 .. 2048.  range = R: a power of two, 2^-4 .. 2^10.  The table covers [-R, R) on both axes.
+ * table: 3*B*B + 1 int64 = count[B*B], sum_u[B*B], sum_v[B*B], outside; the bin of (iu, iv) is iv*B + iu.
+ * The bin of a vector (this arithmetic is the definition): tu = (u + R) * (B / 2R), the sum rounded to f32, the product
+ * exact (the scale is a power of two); tv likewise from v.  In range iff 0 <= tu < B and 0 <= tv < B: NaN, +-inf, u = R and
+ * a u whose u + R rounds up to 2R are outside.  iu = (int)floorf(tu), iv = (int)floorf(tv).
+ * In range: count += 1, sum_u += llrint((double)u * 65536), sum_v += llrint((double)v * 65536).  Otherwise outside += 1 and
+ * nothing else.  Integer adds only: two runs give equal bits whatever the order of the adds, and tables of batches, clips
+ * or ranks merge by plain addition.
+ * ------------------------------------------------------------------------------------------ */
+#define OFC_UV_HIST_SHARE 2048      /* consecutive vectors a work-group of the kernel takes at a time */
+#define OFC_UV_HIST_MAX_GRID 2048   /* most work-groups of a launch: above SHARE * MAX_GRID vectors they take several shares */
+/* flow_dev: n vectors [n][2] f32 on the device (8-byte aligned); table_dev: the table on the device.  The caller zeroes it;
+ * the call adds to what is there, and returns when the adds are done.  n = 0 is a no-op.
+ * OFC_EINVAL: bins or range outside the above, n < 0, a null pointer (flow_dev may be NULL when n = 0).  Everything is
+ * checked before anything is launched. */
+int ofc_uv_hist_accum_dev(int device, const float *flow_dev, int64_t n, int bins, float range, int64_t *table_dev);
+/* the same with host buffers; it WRITES table_host: zero, accumulate, copy out */
+int ofc_uv_hist(int device, const float *flow_host, int64_t n, int bins, float range, int64_t *table_host);
+/* Measurement hook: average duration, by HIP events on the kernel's stream, of `iters` launches of the histogram kernel
+ * over flow_dev (n >= 1), two warm-up launches before them.  The table is the hook's own, zeroed once, untimed. */
+int ofc_bench_uv_hist(int device, const float *flow_dev, int64_t n, int bins, float range, int iters, float *ms_per_launch);
 
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between

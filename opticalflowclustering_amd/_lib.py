@@ -14,6 +14,8 @@ OFC_OK, OFC_EINVAL, OFC_ENODEV, OFC_EHIP, OFC_ENOMEM, OFC_ENOTREADY, OFC_EUNSUPP
 U8, F32, F64 = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 KPP_CHUNK = 1024          # OFC_KPP_CHUNK: samples per partial sum of the seeding's two-level cumulative sum
+UV_HIST_SHARE = 2048      # OFC_UV_HIST_SHARE: consecutive vectors a work-group of the histogram kernel takes at a time
+UV_HIST_MAX_GRID = 2048   # OFC_UV_HIST_MAX_GRID: most work-groups of one histogram launch
 
 
 class OfcError(RuntimeError):
@@ -112,10 +114,15 @@ _PROTOS = {
     "ofc_stream_finish": ([_vp, _vp, _i, _ip], _i),
     "ofc_stream_set_model": ([_vp, _i, _vp, _vp, _i], _i),
     "ofc_stream_finish_clusters": ([_vp, _vp, _vp, _vp, _i, _ip], _i),
+    "ofc_stream_set_histogram": ([_vp, _i, _f], _i),
+    "ofc_stream_read_histogram": ([_vp, _vp, _i], _i),
     "ofc_stream_destroy": ([_vp], None),
     "ofc_grid_cell_mean_flow": ([_i, _vp, _i, _i, _i, _i, _vp], _i),
     "ofc_grid_label_counts_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "ofc_grid_assign_counts_dev": ([_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "ofc_uv_hist_accum_dev": ([_i, _vp, _i64, _i, _f, _vp], _i),
+    "ofc_uv_hist": ([_i, _vp, _i64, _i, _f, _vp], _i),
+    "ofc_bench_uv_hist": ([_i, _vp, _i64, _i, _f, _i, C.POINTER(_f)], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

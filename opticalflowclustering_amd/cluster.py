@@ -194,6 +194,9 @@ def kmeans_plusplus_dev(X_ptr, dtype, N, d, n_clusters, random_state=None, n_loc
 
 
 class KMeans:
+    """n_init is stored for sklearn's signature and ignored: fit() runs once from `init`.  Restarts are offered where they
+    cost next to nothing, on the (u,v) histogram of a field: uvhist.UVHistogram.fit(k, n_init=...)."""
+
     def __init__(self, n_clusters=8, *, init="seeded-rows", n_init=1, max_iter=300, tol=1e-4,
                  random_state=0, device=0, **_ignored):
         self.n_clusters, self.init, self.n_init = int(n_clusters), init, n_init

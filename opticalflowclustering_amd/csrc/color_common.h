@@ -42,6 +42,10 @@ int launch_grid_cell_mean_flow(const float *flow, int W, int H, int npair, int r
 // grid_labels.hip: per (frame, cell, label < k) pixel counts [n_frames][rows*cols][k] and, with flow, (u, v) sums [..][k][2]
 int launch_grid_label_counts(const uint8_t *labels, const float *flow, int W, int H, int n_frames, int rows, int cols, int k,
                              int32_t *counts, double *sums, hipStream_t s);
+// uv_hist.hip: OFC_OK, or OFC_EINVAL with the message set when bins / range are not what ofc_uv_hist_accum_dev accepts
+int uv_hist_check(int bins, float range);
+// flow [n][2] f32, n >= 1, added to table (3*bins*bins + 1 int64: count, sum_u, sum_v, outside); bins and range checked
+int launch_uv_hist(const float *flow, int64_t n, int bins, float range, int64_t *table, hipStream_t s);
 int launch_sliding_cosine(const double *a, int na, const double *b, int nwin, double *sims, int all_int, hipStream_t s);
 int launch_synth_frames(uint8_t *frames, int W, int H, int nframes, int t0, const SynthParams &sp, hipStream_t s);
 

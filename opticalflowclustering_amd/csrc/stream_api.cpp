@@ -2,7 +2,8 @@
 // (BASELINE.json configs[4] shape).  Two slots; while slot A's batch computes on the engine's stream, the host fills
 // slot B's pinned buffer and its hipMemcpyAsync runs on the copy stream.  Consecutive batches overlap by one frame.
 // With a model (ofc_stream_set_model) every batch's field is also labelled against it and counted per cell, behind the
-// cell means on the compute stream, while the field is still where the flow left it.
+// cell means on the compute stream, while the field is still where the flow left it.  With a histogram
+// (ofc_stream_set_histogram) it is added to the stream's (u,v) table behind those, by uv_hist.hip's kernel.
 #include "color_common.h"
 #include "lloyd_common.h"
 
@@ -32,6 +33,10 @@ struct ofc_stream {
     DevBuf model;                      // LloydState
     DevBuf counts, sums;               // [max_pairs][rows*cols][k] int32, [...][k][2] f64 (with_sums): grow with `cells`
     size_t clusters_cap = 0;           // pairs
+    // the (u,v) histogram, when there is one (hist_bins > 0): every batch adds to it, a finish leaves it alone
+    int hist_bins = 0;
+    float hist_range = 0.f;
+    DevBuf hist;                       // 3 * hist_bins^2 + 1 int64
 };
 
 namespace {
@@ -75,7 +80,8 @@ int ensure_clusters(ofc_stream *s, int need_pairs)
     return OFC_OK;
 }
 
-// submit the frames packed in slot `i` (n >= 2): async upload, flow, cell means, and with a model the cluster counts
+// submit the frames packed in slot `i` (n >= 2): async upload, flow, cell means, with a model the cluster counts, and with
+// a histogram the batch's share of the table
 int submit(ofc_stream *s, int i)
 {
     ofc_stream::Slot &sl = s->slot[i];
@@ -95,6 +101,9 @@ int submit(ofc_stream *s, int i)
                                           s->k, s->counts.as<int32_t>() + at,
                                           s->with_sums ? s->sums.as<double>() + at * 2 : nullptr, s->compute));
     }
+    if (s->hist_bins)
+        OFC_TRY(launch_uv_hist(sl.flows.as<float>(), (int64_t)P * npair, s->hist_bins, s->hist_range, s->hist.as<int64_t>(),
+                               s->compute));
     OFC_HIP(hipEventRecord(sl.done, s->compute));
     sl.busy = true;
     sl.inflight_pairs = npair;
@@ -241,6 +250,47 @@ int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts,
         if (sums) OFC_HIP(hipMemcpy(sums, s->sums.p, sizeof(double) * 2 * cells * s->k * n, hipMemcpyDeviceToHost));
     }
     s->pairs_submitted = 0;
+    return OFC_OK;
+}
+
+int ofc_stream_set_histogram(ofc_stream_t *s, int bins, float range)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (bins != 0) OFC_TRY(uv_hist_check(bins, range));
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: set the histogram on a fresh stream or straight after a finish");
+    OFC_TRY(ensure_device(s->device));
+    if (bins == 0) {
+        s->hist.release();
+        s->hist_bins = 0;
+        s->hist_range = 0.f;
+        return OFC_OK;
+    }
+    if (bins == s->hist_bins && range == s->hist_range) return OFC_OK;      // the table stays, with what is in it
+    DevBuf nb;
+    OFC_TRY(nb.alloc(sizeof(int64_t) * (3 * (size_t)bins * bins + 1)));
+    OFC_HIP(hipMemsetAsync(nb.p, 0, nb.bytes, s->compute));
+    OFC_HIP(hipStreamSynchronize(s->compute));
+    std::swap(s->hist.p, nb.p);
+    std::swap(s->hist.bytes, nb.bytes);
+    s->hist_bins = bins;
+    s->hist_range = range;
+    return OFC_OK;
+}
+
+int ofc_stream_read_histogram(ofc_stream_t *s, int64_t *table_host, int reset)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->hist_bins > 0, "the stream has no histogram (ofc_stream_set_histogram)");
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: read the histogram straight after a finish");
+    OFC_TRY(ensure_device(s->device));
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    if (table_host) OFC_HIP(hipMemcpy(table_host, s->hist.p, s->hist.bytes, hipMemcpyDeviceToHost));
+    if (reset) {
+        OFC_HIP(hipMemsetAsync(s->hist.p, 0, s->hist.bytes, s->compute));
+        OFC_HIP(hipStreamSynchronize(s->compute));
+    }
     return OFC_OK;
 }
 

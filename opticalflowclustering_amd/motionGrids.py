@@ -9,12 +9,18 @@ gives that cluster's direction (computeOpticalFlowModule.py:25-33: hue = angle /
     python -m opticalflowclustering_amd.motionGrids --path CLIP -c 5 -f OUT.csv --save-model centres.npy
     python -m opticalflowclustering_amd.motionGrids --path OTHER -c 5 -f OTHER.csv --model centres.npy
     python -m opticalflowclustering_amd.motionGrids --path LONG -c 5 -f LONG.csv --model centres.npy --stream
+    python -m opticalflowclustering_amd.motionGrids --path LONG -c 5 -f LONG.csv --fit-stream --n-init 4
 
 With --stream the clip is never resident: its frames are read one at a time and pushed through a FlowStream that carries
 the model, which labels and counts every batch's field on the device while it is there (FlowStream.finish_clusters), so
 the clip may be longer than memory.  A stream has no field mean before it ends: it labels against mean (0, 0), as
 KMeans.predict does, where ClipPipeline.assign centres the arithmetic by the field's mean.  The two agree except where a
 pixel's two nearest centres tie to the rounding of the expanded form; bit equality of the two routes is not promised.
+
+With --fit-stream the clip is never resident either, and the model is fitted on it all the same, in two passes over the
+file.  Pass 1 pushes the frames through a FlowStream that adds every pair's field to a (u,v) histogram (uvhist.py) and fits
+the centres on that table (-c, --seed, an --init file and --n-init restarts apply); pass 2 is the --stream route with those
+centres.  Vectors outside --hist-range take no part in the fit; their share is printed.
 """
 import argparse
 import os
@@ -91,7 +97,25 @@ def parse_arguments(argv=None):
     ap.add_argument("--stream", action="store_true",
                     help="with --model: read the clip frame by frame and count on a FlowStream; the clip is never resident")
     ap.add_argument("--batch-pairs", type=int, default=8, help="frame pairs per batch of the --stream route")
+    ap.add_argument("--fit-stream", action="store_true",
+                    help="fit on the clip's (u,v) histogram, built on a FlowStream, then count as --stream does: two passes "
+                         "over the file, the clip is never resident")
+    ap.add_argument("--hist-bins", type=int, default=1024, help="bins per axis of the --fit-stream histogram (a power of two)")
+    ap.add_argument("--hist-range", type=float, default=32.0,
+                    help="the --fit-stream histogram covers [-RANGE, RANGE) px on both axes (a power of two)")
+    ap.add_argument("--n-init", type=int, default=1, help="k-means++ restarts of the --fit-stream fit; the lowest inertia wins")
     args = ap.parse_args(argv)
+    if args.fit_stream:
+        for flag, given in (("--model", args.model), ("--stream", args.stream), ("--weights", args.weights)):
+            if given:
+                ap.error(f"--fit-stream fits its own model on an unweighted stream: it cannot be combined with {flag}")
+        from .uvhist import check_params
+        try:
+            check_params(args.hist_bins, args.hist_range)
+        except ValueError as e:
+            ap.error(str(e))
+        if args.n_init < 1:
+            ap.error("--n-init must be at least 1")
     if args.stream and not args.model:
         ap.error("--stream applies a model to arriving frames and cannot fit one: it requires --model")
     if args.batch_pairs < 1:
@@ -147,11 +171,39 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0):
             fs.close()
 
 
+def stream_histogram(path, bins, range, rows=14, cols=25, batch_pairs=8, device=0):
+    """the (u,v) histogram (uvhist.UVHistogram) of a clip that is read frame by frame and never resident"""
+    from .stream import FlowStream
+    fs, n = None, 0
+    try:
+        for gray in gray_frames(path, device):
+            if fs is None:
+                fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, histogram=(bins, range))
+            fs.push(gray)
+            n += 1
+        if n < 2:
+            raise RuntimeError(f"{path!r} has {n} frame(s); a flow field needs two")
+        fs.finish()
+        return fs.histogram()
+    finally:
+        if fs is not None:
+            fs.close()
+
+
 def main(argv=None):
     args = parse_arguments(argv)
     k = args.clusters
     given = _load_centres(args.model, k, "--model") if args.model else \
         _load_centres(args.init, k, "--init") if args.init != "k-means++" else None
+    if args.fit_stream:
+        hist = stream_histogram(args.path, args.hist_bins, args.hist_range, args.rows, args.cols, args.batch_pairs, args.device)
+        total = hist.n + hist.outside
+        print(f"histogram: {hist.n} vectors in {int(np.count_nonzero(hist.counts))} bins, {hist.outside} outside "
+              f"[-{args.hist_range:g}, {args.hist_range:g}) px ({100.0 * hist.outside / max(total, 1):.4f} %)")
+        centers, _, _ = hist.fit(k, init="k-means++" if given is None else given, random_state=args.seed, n_init=args.n_init,
+                                 device=args.device)
+        counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device)
+        return _write_outputs(args, counts, centers)
     if args.stream:
         centers = given
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device)

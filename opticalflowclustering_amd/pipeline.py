@@ -216,6 +216,22 @@ class ClipPipeline:
             if sm is not None:
                 sm.free()
 
+    def uv_histogram(self, bins=1024, range=32.0):
+        """the (u,v) histogram of the resident field (ofc_uv_hist_accum_dev: one read of the field where the flow left it;
+        only the table leaves the device) -> uvhist.UVHistogram, whose fit() stands in for run_kmeans on this field and
+        takes n_init restarts.  Rank-local: this rank's pairs, no collective; the ranks' tables merge by addition."""
+        from .uvhist import UVHistogram, check_params, table_len
+        bins, range = check_params(bins, range)
+        self.sync()
+        tab = DeviceBuffer(table_len(bins) * 8, self.device)
+        try:
+            tab.zero()
+            check(load().ofc_uv_hist_accum_dev(self.device, C.c_void_p(self.flows.ptr), self.n_pairs * self.W * self.H, bins,
+                                               range, C.c_void_p(tab.ptr)))
+            return UVHistogram(bins, range, tab.download((table_len(bins),), np.int64))
+        finally:
+            tab.free()
+
     def sample_uv(self, idx):
         """host copy of a few (u,v) rows (for choosing the initial centres)"""
         out = np.empty((len(idx), 2), np.float32)

@@ -111,6 +111,13 @@ def bench_lloyd_sweep_w(X_ptr, w_ptr, w_dtype, N, centers, mean, iters=10, devic
     return ms.value
 
 
+def bench_uv_hist(flow_ptr, n, bins=1024, range=32.0, iters=10, device=0):
+    """ms per launch of the (u,v) histogram kernel over a resident field of n vectors (ofc_bench_uv_hist)"""
+    ms = C.c_float()
+    check(load().ofc_bench_uv_hist(device, C.c_void_p(flow_ptr), n, bins, range, iters, C.byref(ms)))
+    return ms.value
+
+
 def flow_weights_dev(flow_ptr, n, kind, thr, w_ptr, device=0):
     """sample weights from a resident (u,v) field (ofc_flow_weights_dev): kind 'magnitude' -> |(u,v)|, 'moving' -> 1 where
     |(u,v)| >= thr, else 0; n f32 weights written to w_ptr"""

@@ -3,7 +3,9 @@ packed into pinned ring buffers, uploaded with hipMemcpyAsync on a copy stream w
 and reduced to the grid-cell averaged flow (rows*cols (u,v) means per pair).  k-means over those vectors is then a
 small streaming-Lloyd problem (cluster.KMeans).  With a model (fitted (k,2) centres) the stream also applies it: every
 pair's field is labelled against the centres and counted per grid cell on the device while it is still there
-(finish_clusters), so a fit can be deployed on footage that keeps arriving or is longer than memory."""
+(finish_clusters), so a fit can be deployed on footage that keeps arriving or is longer than memory.  With a histogram
+(histogram=(bins, range)) every pair's field is also added to the stream's (u,v) table (uvhist.py), so a model can be fitted
+on such footage too: histogram().fit(k)."""
 import ctypes as C
 
 import numpy as np
@@ -12,7 +14,8 @@ from ._lib import FbParams, check, load, ptr
 
 
 class FlowStream:
-    def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False):
+    def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False,
+                 histogram=None):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
@@ -20,8 +23,33 @@ class FlowStream:
         self._h = h
         self.pushed = 0
         self.k, self.sums = 0, False
+        self.hist = None                    # (bins, range) of the stream's histogram, or None
         if centers is not None:
             self.set_model(centers, mean, sums)
+        if histogram is not None:
+            self.set_histogram(*histogram)
+
+    def set_histogram(self, bins, range=32.0):
+        """from the next batch on, add every pair's field to the stream's (u,v) histogram (ofc_stream_set_histogram, the
+        kernel of uvhist.uv_histogram); bins=None or 0 removes it.  Only on a stream that holds no frame and no undelivered
+        result, as set_model; ValueError otherwise, and nothing changes.  The same (bins, range) again keeps the table."""
+        if not bins:
+            check(load().ofc_stream_set_histogram(self._h, 0, 0.0))
+            self.hist = None
+            return
+        from .uvhist import check_params
+        bins, range = check_params(bins, range)
+        check(load().ofc_stream_set_histogram(self._h, bins, range))
+        self.hist = (bins, range)
+
+    def histogram(self, reset=True):
+        """-> uvhist.UVHistogram of every pair since the table was last reset (ofc_stream_read_histogram); with reset the
+        table then starts over, without it the next clips add to it.  Straight after finish() / finish_clusters() only (or on
+        a fresh stream: an empty table); ValueError otherwise, and on a stream without a histogram."""
+        from .uvhist import UVHistogram, table_len
+        table = np.empty(table_len(self.hist[0]) if self.hist else 1, np.int64)
+        check(load().ofc_stream_read_histogram(self._h, ptr(table), int(bool(reset))))
+        return UVHistogram(self.hist[0], self.hist[1], table)
 
     def set_model(self, centers, mean=None, sums=False):
         """from the next batch on, label every pair's field against `centers` ((k,2), un-centred; None removes the model)
