@@ -511,6 +511,77 @@ int ofc_uv_hist(int device, const float *flow_host, int64_t n, int bins, float r
 int ofc_bench_uv_hist(int device, const float *flow_dev, int64_t n, int bins, float range, int iters, float *ms_per_launch);
 
 /* ------------------------------------------------------------------------------------------
+ * Camera motion: per frame pair, a translation or an affine model of the flow field, fitted by iteratively re-selected least
+ * squares and subtracted, so that what follows the flow (the Lloyd fits and their weights, the histogram, the stream's model,
+ * the cell summaries) sees the scene's motion and not the camera's.  No reference counterpart.
+ * Definition (this arithmetic is the definition).  Field (u, v)[y][x], W x H.  X = 2x - (W-1), Y = 2y - (H-1): twice the
+ * offset from the frame centre, always integers.  Model p = (p0..p5), f64, in pixels and pixels per pixel about the centre:
+ *   u^ = p0 + p1 X/2 + p2 Y/2,  v^ = p3 + p4 X/2 + p5 Y/2,  each evaluated as one chain fma(p2, 0.5*Y, fma(p1, 0.5*X, p0)) in f64.
+ * kind 1 "translation" fixes p1 = p2 = p4 = p5 = 0; kind 2 "affine" fits all six.
+ * Valid: u and v finite and |u|, |v| < 1024.  Any other vector is outside: counted, never used.
+ * Fixed point: qu = llrint((double)u * 65536), qv likewise (the histogram's rule).
+ * Moments over a set S of valid pixels, thirteen int64:
+ *   n, SX, SY, SXX, SXY, SYY, Squ, SXqu, SYqu, Sqv, SXqv, SYqv, outside
+ * (sums of 1, X, Y, X X, X Y, Y Y, qu, X qu, Y qu, qv, X qv, Y qv over S; outside counts the pair's vectors that are not
+ * valid, whatever S).  Integers only: any order of the adds gives equal bits.  They fit int64 iff W * H * max(W, H) < 2^37
+ * (3840 x 2160 passes, 8192 x 8192 does not).
+ * Rounds.  Round 0: S = every valid pixel; p = the least-squares solution of the moments.  Round t = 1..T with threshold c_t
+ * px: S = valid pixels with (u - u^)^2 + (v - v^)^2 <= c_t^2, compared in f64 under round t-1's model; solve again.  If
+ * n < 3 (translation: n < 1) or a pivot of the solve is not positive, the pair keeps the model of the round before, gets
+ * status 1 and takes no further rounds; in round 0 the model is all zeros and the status 2.  Status 0: every round solved.
+ * A fit with kind 1 forms only n, Squ, Sqv and outside; the other moments of its history are 0.
+ * Solve: the exact least-squares solution of the integer moments, computed in f64: the 3 x 3 normal matrix over
+ * (1, X sx, Y sy), sx = 2^-e with e = floor((floor(log2 SXX) - floor(log2 n)) / 2) (1 when SXX = 0) and sy likewise from SYY,
+ * so its entries are O(n); factored as L D L^T (Cholesky without the square roots; the pivots are D's entries); u and v
+ * share the factors.  One function (csrc/motion_model.h) runs in the kernel and on the host: equal bits.
+ * Subtract: u' = (float)((double)u - u^), v' likewise; a vector with a non-finite component passes through unchanged.
+ * thresholds: T doubles (c_1..c_T), T in 0..8, each finite and positive.  At most 65535 pairs per call (OFC_EUNSUPPORTED).
+ * ------------------------------------------------------------------------------------------ */
+/* Host only, no device is touched: OFC_OK if fields of W x H can be fitted with `kind`.  OFC_EINVAL: kind not 1 or 2, W or
+ * H < 1, kind 2 with W < 2 or H < 2.  OFC_EUNSUPPORTED: W * H * max(W, H) >= 2^37.  Every call below decides by it first. */
+int ofc_motion_check(int W, int H, int kind);
+/* Host only: the solve above on given moments.  p receives the model and *status 0, or zeros and *status 1 when the moments
+ * cannot be solved.  OFC_EINVAL: a null pointer, kind not 1 or 2. */
+int ofc_motion_solve(const int64_t m[13], int kind, double p[6], int *status);
+/* One launch of the moment reduction over flow_dev [npair][H][W][2] f32 (8-byte aligned) -> moments_host [npair][13].
+ * models NULL: S = every valid pixel.  Otherwise models [npair][6] (finite) and c [npair] (finite, positive): S as in a
+ * round under that model and threshold.  Always all thirteen.  The tests' handle on the kernel. */
+int ofc_motion_moments_dev(int device, const float *flow_dev, int W, int H, int npair, const double *models, const double *c,
+                           int64_t *moments_host);
+/* The whole fit, T + 1 moment launches and T + 1 solves chained on one stream with no host round trip between rounds.
+ * models_host [npair][6], status_host [npair]; history_models [(T+1)][npair][6] and history_moments [(T+1)][npair][13] may
+ * each be NULL: what every round solved from and found.  A pair that takes no further rounds repeats its kept model, with
+ * zero moments, in the rounds it does not take. */
+int ofc_motion_fit_dev(int device, const float *flow_dev, int W, int H, int npair, int kind, const double *thresholds, int T,
+                       double *models_host, int *status_host, double *history_models, int64_t *history_moments);
+/* dst_dev = flow_dev minus the models (models_host [npair][6], finite); dst_dev may equal flow_dev.  Returns when done. */
+int ofc_motion_subtract_dev(int device, const float *flow_dev, int W, int H, int npair, const double *models_host,
+                            float *dst_dev);
+/* ofc_motion_fit_dev with a host field: upload, fit, download */
+int ofc_motion_fit(int device, const float *flow_host, int W, int H, int npair, int kind, const double *thresholds, int T,
+                   double *models_host, int *status_host, double *history_models, int64_t *history_moments);
+/* the same, and residual_host [npair][H][W][2] = the field minus the fitted models */
+int ofc_motion_compensate(int device, const float *flow_host, int W, int H, int npair, int kind, const double *thresholds,
+                          int T, float *residual_host, double *models_host, int *status_host, double *history_models,
+                          int64_t *history_moments);
+/* A stream that removes the camera: from the next batch on, every pair's field is fitted and the model subtracted in place,
+ * on the compute stream between the flow and the cell means, so the cell means, the model's counts and the histogram all
+ * see the residual field.  kind 0 removes the camera: the stream then launches exactly what a stream that never had one
+ * launches.  Same precondition as ofc_stream_set_model (no frame and no undelivered result; otherwise OFC_EINVAL and
+ * nothing changes); kind, thresholds, T and the frame size as for ofc_motion_fit_dev. */
+int ofc_stream_set_camera(ofc_stream_t *s, int kind, const double *thresholds, int T);
+/* models [n][6] and status [n] (each may be NULL) of the n pairs the LAST finish delivered, in their order.  A finish keeps
+ * that count when it empties the stream, so this is valid straight after a finish (either form) and until the next frame
+ * is pushed: with frames held, OFC_EINVAL.  max_pairs < n: OFC_EINVAL, nothing written.  A finish that was refused for lack
+ * of room keeps the fits with the results.  OFC_EINVAL without a camera. */
+int ofc_stream_read_camera(ofc_stream_t *s, double *models, int *status, int max_pairs);
+/* Measurement hook: average duration, by HIP events, of `iters` launches over flow_dev [npair][H][W][2], two warm-up launches
+ * before them, under round 0's affine model and c = 4 px.  what = 0: the moment kernel, all thirteen; 1: its translation
+ * form (n, Squ, Sqv, outside); 2: the solve kernel; 3: the subtraction into a buffer of the hook's own; 4: a whole affine
+ * fit with thresholds (4, 2, 1): four moment launches and four solves. */
+int ofc_bench_motion(int device, const float *flow_dev, int W, int H, int npair, int what, int iters, float *ms_per_launch);
+
+/* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.
  * sims has n_large-n_small+1 entries; 0 where either norm is 0.  Integer-valued input (the hue columns) is summed exactly

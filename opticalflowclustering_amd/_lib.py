@@ -123,6 +123,16 @@ _PROTOS = {
     "ofc_uv_hist_accum_dev": ([_i, _vp, _i64, _i, _f, _vp], _i),
     "ofc_uv_hist": ([_i, _vp, _i64, _i, _f, _vp], _i),
     "ofc_bench_uv_hist": ([_i, _vp, _i64, _i, _f, _i, C.POINTER(_f)], _i),
+    "ofc_motion_check": ([_i, _i, _i], _i),
+    "ofc_motion_solve": ([_vp, _i, _vp, _ip], _i),
+    "ofc_motion_moments_dev": ([_i, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "ofc_motion_fit_dev": ([_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp], _i),
+    "ofc_motion_subtract_dev": ([_i, _vp, _i, _i, _i, _vp, _vp], _i),
+    "ofc_motion_fit": ([_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp], _i),
+    "ofc_motion_compensate": ([_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "ofc_stream_set_camera": ([_vp, _i, _vp, _i], _i),
+    "ofc_stream_read_camera": ([_vp, _vp, _vp, _i], _i),
+    "ofc_bench_motion": ([_i, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

@@ -3,9 +3,12 @@
 // slot B's pinned buffer and its hipMemcpyAsync runs on the copy stream.  Consecutive batches overlap by one frame.
 // With a model (ofc_stream_set_model) every batch's field is also labelled against it and counted per cell, behind the
 // cell means on the compute stream, while the field is still where the flow left it.  With a histogram
-// (ofc_stream_set_histogram) it is added to the stream's (u,v) table behind those, by uv_hist.hip's kernel.
+// (ofc_stream_set_histogram) it is added to the stream's (u,v) table behind those, by uv_hist.hip's kernel.  With a camera
+// (ofc_stream_set_camera) every pair's camera motion is fitted and subtracted in place between the flow and the cell means
+// (motion_model.hip), so all of the above see the residual field.
 #include "color_common.h"
 #include "lloyd_common.h"
+#include "motion_model.h"
 
 #include <memory>
 
@@ -37,6 +40,12 @@ struct ofc_stream {
     int hist_bins = 0;
     float hist_range = 0.f;
     DevBuf hist;                       // 3 * hist_bins^2 + 1 int64
+    // the camera, when there is one (cam_kind > 0): every pair's fit, kept past the finish until the next clip's batches overwrite it
+    int cam_kind = 0, cam_T = 0;
+    double cam_thr[8] = {};
+    DevBuf cam_rec, cam_partial;       // MotionRec [max_pairs], grows with `cells`; the moment kernel's partials of a batch
+    size_t cam_cap = 0;                // pairs
+    int cam_pairs = 0;                 // pairs of the last finish: what ofc_stream_read_camera delivers
 };
 
 namespace {
@@ -80,8 +89,25 @@ int ensure_clusters(ofc_stream *s, int need_pairs)
     return OFC_OK;
 }
 
-// submit the frames packed in slot `i` (n >= 2): async upload, flow, cell means, with a model the cluster counts, and with
-// a histogram the batch's share of the table
+// room for the camera fits of need_pairs pairs: same growth as ensure_cells, what was fitted so far is kept
+int ensure_camera(ofc_stream *s, int need_pairs)
+{
+    if ((size_t)need_pairs <= s->cam_cap) return OFC_OK;
+    const size_t cap = std::max<size_t>(need_pairs, s->cam_cap ? s->cam_cap * 2 : 256);
+    DevBuf nb;
+    OFC_TRY(nb.alloc(cap * sizeof(MotionRec)));
+    if (s->cam_rec.p && s->pairs_submitted) {
+        OFC_HIP(hipStreamSynchronize(s->compute));
+        OFC_HIP(hipMemcpy(nb.p, s->cam_rec.p, (size_t)s->pairs_submitted * sizeof(MotionRec), hipMemcpyDeviceToDevice));
+    }
+    std::swap(s->cam_rec.p, nb.p);
+    std::swap(s->cam_rec.bytes, nb.bytes);
+    s->cam_cap = cap;
+    return OFC_OK;
+}
+
+// submit the frames packed in slot `i` (n >= 2): async upload, flow, with a camera its fit and subtraction, cell means,
+// with a model the cluster counts, and with a histogram the batch's share of the table
 int submit(ofc_stream *s, int i)
 {
     ofc_stream::Slot &sl = s->slot[i];
@@ -89,10 +115,17 @@ int submit(ofc_stream *s, int i)
     const size_t P = (size_t)s->W * s->H;
     OFC_TRY(ensure_cells(s, s->pairs_submitted + npair));
     if (s->k) OFC_TRY(ensure_clusters(s, s->pairs_submitted + npair));
+    if (s->cam_kind) OFC_TRY(ensure_camera(s, s->pairs_submitted + npair));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
     OFC_TRY(ofc_flow_calc_frames_dev(s->flow, sl.frames.as<uint8_t>(), sl.n_frames, sl.flows.as<float>()));
+    if (s->cam_kind) {
+        MotionRec *rec = s->cam_rec.as<MotionRec>() + s->pairs_submitted;
+        OFC_TRY(motion_fit_async(sl.flows.as<float>(), s->W, s->H, npair, s->cam_kind, s->cam_thr, s->cam_T, rec,
+                                 s->cam_partial.as<int64_t>(), nullptr, nullptr, s->compute));
+        OFC_TRY(launch_motion_subtract(sl.flows.as<float>(), sl.flows.as<float>(), s->W, s->H, npair, rec, s->compute));
+    }
     float *dst = s->cells.as<float>() + (size_t)s->pairs_submitted * 2 * s->rows * s->cols;
     OFC_TRY(launch_grid_cell_mean_flow(sl.flows.as<float>(), s->W, s->H, npair, s->rows, s->cols, dst, s->compute));
     if (s->k) {
@@ -201,6 +234,7 @@ int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pai
         OFC_HIP(hipMemcpy(cell_uv, s->cells.p, sizeof(float) * 2 * s->rows * s->cols * (size_t)s->pairs_submitted,
                           hipMemcpyDeviceToHost));
     }
+    s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -249,6 +283,7 @@ int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts,
         if (counts) OFC_HIP(hipMemcpy(counts, s->counts.p, sizeof(int32_t) * cells * s->k * n, hipMemcpyDeviceToHost));
         if (sums) OFC_HIP(hipMemcpy(sums, s->sums.p, sizeof(double) * 2 * cells * s->k * n, hipMemcpyDeviceToHost));
     }
+    s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -290,6 +325,51 @@ int ofc_stream_read_histogram(ofc_stream_t *s, int64_t *table_host, int reset)
     if (reset) {
         OFC_HIP(hipMemsetAsync(s->hist.p, 0, s->hist.bytes, s->compute));
         OFC_HIP(hipStreamSynchronize(s->compute));
+    }
+    return OFC_OK;
+}
+
+int ofc_stream_set_camera(ofc_stream_t *s, int kind, const double *thresholds, int T)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (kind != 0) OFC_TRY(motion_fit_check(s->W, s->H, kind, thresholds, T));
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: set the camera on a fresh stream or straight after a finish");
+    OFC_TRY(ensure_device(s->device));
+    s->cam_pairs = 0;
+    if (kind == 0) {
+        s->cam_rec.release();
+        s->cam_partial.release();
+        s->cam_cap = 0;
+        s->cam_kind = 0;
+        s->cam_T = 0;
+        return OFC_OK;
+    }
+    // the partials of the largest batch at the most work-groups per pair any batch size gets
+    size_t most = 0;
+    for (int n = 1; n <= s->batch; n++) most = std::max(most, (size_t)motion_groups(s->W, s->H, n) * n);
+    OFC_TRY(s->cam_partial.alloc(sizeof(int64_t) * MOTION_NMOM * most));
+    s->cam_kind = kind;
+    s->cam_T = T;
+    for (int t = 0; t < T; t++) s->cam_thr[t] = thresholds[t];
+    return OFC_OK;
+}
+
+int ofc_stream_read_camera(ofc_stream_t *s, double *models, int *status, int max_pairs)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->cam_kind > 0, "the stream has no camera (ofc_stream_set_camera)");
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: read the camera straight after a finish");
+    OFC_REQUIRE(max_pairs >= s->cam_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->cam_pairs);
+    OFC_TRY(ensure_device(s->device));
+    if (!s->cam_pairs || (!models && !status)) return OFC_OK;
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    std::vector<MotionRec> rec(s->cam_pairs);
+    OFC_HIP(hipMemcpy(rec.data(), s->cam_rec.p, sizeof(MotionRec) * rec.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < s->cam_pairs; i++) {
+        if (models) memcpy(models + 6 * (size_t)i, rec[i].p, sizeof(double) * 6);
+        if (status) status[i] = rec[i].status;
     }
     return OFC_OK;
 }

@@ -21,6 +21,10 @@ With --fit-stream the clip is never resident either, and the model is fitted on 
 file.  Pass 1 pushes the frames through a FlowStream that adds every pair's field to a (u,v) histogram (uvhist.py) and fits
 the centres on that table (-c, --seed, an --init file and --n-init restarts apply); pass 2 is the --stream route with those
 centres.  Vectors outside --hist-range take no part in the fit; their share is printed.
+
+With --camera translation|affine every pair's camera motion is fitted and removed on the device before anything else looks at
+the field (camera.py), on the resident route, on --stream and on --fit-stream: the clusters then describe the scene and not
+the camera, and --weights moving:0.5 means "moves against the background".  --camera-out writes the (pairs, 6) models.
 """
 import argparse
 import os
@@ -77,6 +81,17 @@ def parse_weights(text):
     raise argparse.ArgumentTypeError(f"weights should be none, magnitude or moving:THR, got {text!r}")
 
 
+def parse_thresholds(text):
+    """'4,2,1' -> (4.0, 2.0, 1.0); '' -> (): the --camera-thresholds, finite and positive, at most eight"""
+    try:
+        thr = tuple(float(t) for t in text.split(",") if t.strip())
+    except ValueError:
+        thr = None
+    if thr is None or len(thr) > 8 or not all(np.isfinite(t) and t > 0 for t in thr):
+        raise argparse.ArgumentTypeError(f"thresholds should be up to eight positive numbers like 4,2,1, got {text!r}")
+    return thr
+
+
 def parse_arguments(argv=None):
     ap = argparse.ArgumentParser(prog="python -m opticalflowclustering_amd.motionGrids", description=__doc__.split("\n\n")[0])
     ap.add_argument("--path", required=True, help="input video (.npy/.npz stack, image directory, or a video with cv2)")
@@ -104,7 +119,15 @@ def parse_arguments(argv=None):
     ap.add_argument("--hist-range", type=float, default=32.0,
                     help="the --fit-stream histogram covers [-RANGE, RANGE) px on both axes (a power of two)")
     ap.add_argument("--n-init", type=int, default=1, help="k-means++ restarts of the --fit-stream fit; the lowest inertia wins")
+    ap.add_argument("--camera", choices=("none", "translation", "affine"), default="none",
+                    help="fit and remove every pair's camera motion before anything else looks at the field")
+    ap.add_argument("--camera-thresholds", type=parse_thresholds, default=(4.0, 2.0, 1.0), metavar="4,2,1",
+                    help="inlier radii in px of the camera fit's re-selection rounds (the default is a guess, not tuned)")
+    ap.add_argument("--camera-out", metavar="FILE.npy", help="write the (pairs, 6) camera models to this .npy file")
     args = ap.parse_args(argv)
+    if args.camera_out and args.camera == "none":
+        ap.error("--camera-out needs --camera translation or --camera affine")
+    args.camera_spec = None if args.camera == "none" else (args.camera, args.camera_thresholds)
     if args.fit_stream:
         for flag, given in (("--model", args.model), ("--stream", args.stream), ("--weights", args.weights)):
             if given:
@@ -153,32 +176,38 @@ def read_gray_frames(path, device=0):
     return np.stack(frames)
 
 
-def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0):
-    """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident"""
+def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None):
+    """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident; camera as
+    FlowStream's, its (pairs, 6) models saved to camera_out"""
     from .stream import FlowStream
     fs, n = None, 0
     try:
         for gray in gray_frames(path, device):
             if fs is None:
-                fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, centers=centers)
+                fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, centers=centers,
+                                camera=camera)
             fs.push(gray)
             n += 1
         if n < 2:
             raise RuntimeError(f"{path!r} has {n} frame(s); a flow field needs two")
-        return fs.finish_clusters()[1]
+        counts = fs.finish_clusters()[1]
+        if camera is not None and camera_out:
+            np.save(camera_out, fs.camera_motion().params)
+        return counts
     finally:
         if fs is not None:
             fs.close()
 
 
-def stream_histogram(path, bins, range, rows=14, cols=25, batch_pairs=8, device=0):
+def stream_histogram(path, bins, range, rows=14, cols=25, batch_pairs=8, device=0, camera=None):
     """the (u,v) histogram (uvhist.UVHistogram) of a clip that is read frame by frame and never resident"""
     from .stream import FlowStream
     fs, n = None, 0
     try:
         for gray in gray_frames(path, device):
             if fs is None:
-                fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, histogram=(bins, range))
+                fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, histogram=(bins, range),
+                                camera=camera)
             fs.push(gray)
             n += 1
         if n < 2:
@@ -196,17 +225,20 @@ def main(argv=None):
     given = _load_centres(args.model, k, "--model") if args.model else \
         _load_centres(args.init, k, "--init") if args.init != "k-means++" else None
     if args.fit_stream:
-        hist = stream_histogram(args.path, args.hist_bins, args.hist_range, args.rows, args.cols, args.batch_pairs, args.device)
+        hist = stream_histogram(args.path, args.hist_bins, args.hist_range, args.rows, args.cols, args.batch_pairs, args.device,
+                                args.camera_spec)
         total = hist.n + hist.outside
         print(f"histogram: {hist.n} vectors in {int(np.count_nonzero(hist.counts))} bins, {hist.outside} outside "
               f"[-{args.hist_range:g}, {args.hist_range:g}) px ({100.0 * hist.outside / max(total, 1):.4f} %)")
         centers, _, _ = hist.fit(k, init="k-means++" if given is None else given, random_state=args.seed, n_init=args.n_init,
                                  device=args.device)
-        counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device)
+        counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
+                               args.camera_out)
         return _write_outputs(args, counts, centers)
     if args.stream:
         centers = given
-        counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device)
+        counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
+                               args.camera_out)
         return _write_outputs(args, counts, centers)
     from .pipeline import ClipPipeline
     frames = read_gray_frames(args.path, args.device)
@@ -215,6 +247,10 @@ def main(argv=None):
     try:
         pipe.upload_frames(frames)
         pipe.run_flow()
+        if args.camera_spec:
+            motion = pipe.compensate_camera(*args.camera_spec)
+            if args.camera_out:
+                np.save(args.camera_out, motion.params)
         if args.model:
             centers = given
             pipe.assign(centers)

@@ -232,6 +232,28 @@ class ClipPipeline:
         finally:
             tab.free()
 
+    def compensate_camera(self, model="affine", thresholds=(4.0, 2.0, 1.0)):
+        """fit every pair's camera motion on the resident field and subtract it there (camera.py: ofc_motion_fit_dev, then
+        ofc_motion_subtract_dev in place) -> camera.CameraMotion.  What follows -- run_kmeans and its weights, uv_histogram,
+        assign, cell_clusters(centers=) -- then sees the motion against the background.  The flow engine's column sums
+        and the resident labels belong to the field as it was: the next fit sweeps for its own column sums, and
+        cell_clusters() without centers= is refused until run_kmeans() or assign() has labelled the residual.
+        The default thresholds are a guess, not tuned on any footage.  Rank-local under a communicator: a pair depends on
+        itself alone, no collective."""
+        from . import camera as cam
+        kind, thr, T = cam.camera_args(model, thresholds)
+        self.sync()
+        n = self.n_pairs
+        params, status = np.zeros((n, 6)), np.zeros(n, np.int32)
+        moments = np.zeros((T + 1, n, cam.NMOM), np.int64)
+        fp = C.c_void_p(self.flows.ptr)
+        check(load().ofc_motion_fit_dev(self.device, fp, self.W, self.H, n, kind, _lib.ptr(thr), T, _lib.ptr(params),
+                                        _lib.ptr(status), None, _lib.ptr(moments)))
+        self._sums_valid = False
+        self._label_k = None
+        check(load().ofc_motion_subtract_dev(self.device, fp, self.W, self.H, n, _lib.ptr(params), fp))
+        return cam.motion_from_history(params, status, moments, model)
+
     def sample_uv(self, idx):
         """host copy of a few (u,v) rows (for choosing the initial centres)"""
         out = np.empty((len(idx), 2), np.float32)

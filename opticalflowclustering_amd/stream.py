@@ -5,7 +5,8 @@ small streaming-Lloyd problem (cluster.KMeans).  With a model (fitted (k,2) cent
 pair's field is labelled against the centres and counted per grid cell on the device while it is still there
 (finish_clusters), so a fit can be deployed on footage that keeps arriving or is longer than memory.  With a histogram
 (histogram=(bins, range)) every pair's field is also added to the stream's (u,v) table (uvhist.py), so a model can be fitted
-on such footage too: histogram().fit(k)."""
+on such footage too: histogram().fit(k).  With a camera (camera="affine") every pair's camera motion is fitted and subtracted
+on the device straight after the flow (camera.py), and all of the above see the residual field."""
 import ctypes as C
 
 import numpy as np
@@ -15,7 +16,7 @@ from ._lib import FbParams, check, load, ptr
 
 class FlowStream:
     def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False,
-                 histogram=None):
+                 histogram=None, camera=None):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
@@ -28,6 +29,38 @@ class FlowStream:
             self.set_model(centers, mean, sums)
         if histogram is not None:
             self.set_histogram(*histogram)
+        self.camera = None                  # (model, thresholds) of the stream's camera, or None
+        self._last_pairs = 0                # pairs the last finish delivered
+        if camera is not None:
+            self.set_camera(camera)
+
+    def set_camera(self, camera, thresholds=None):
+        """from the next batch on, fit every pair's camera motion and subtract it in place before anything else looks at
+        the field (ofc_stream_set_camera): the cell means, the model's counts and the histogram then see the residual.
+        camera: None (removes it), 'translation', 'affine' or (kind, thresholds); thresholds as camera.compensate's (the
+        default (4.0, 2.0, 1.0) is a guess, not tuned on any footage).  Only on a stream that holds no frame and no
+        undelivered result, as set_model; ValueError otherwise, and nothing changes."""
+        from .camera import camera_args, parse_camera
+        if thresholds is not None and isinstance(camera, str):
+            camera = (camera, thresholds)
+        cam = parse_camera(camera)
+        if cam is None:
+            check(load().ofc_stream_set_camera(self._h, 0, None, 0))
+        else:
+            kind, thr, T = camera_args(*cam)
+            check(load().ofc_stream_set_camera(self._h, kind, ptr(thr), T))
+        self.camera = cam
+        self._last_pairs = 0
+
+    def camera_motion(self):
+        """-> camera.CameraMotion of the pairs the last finish() / finish_clusters() delivered (ofc_stream_read_camera):
+        params (n,6) and status (n,); the stream keeps no moments, so inliers and outside are None.  Straight after a
+        finish only; ValueError once frames are held again, and on a stream without a camera."""
+        from .camera import CameraMotion
+        n = self._last_pairs
+        params, status = np.zeros((max(n, 1), 6)), np.zeros(max(n, 1), np.int32)
+        check(load().ofc_stream_read_camera(self._h, ptr(params), ptr(status), max(n, 1)))
+        return CameraMotion(params[:n], status[:n], None, None)
 
     def set_histogram(self, bins, range=32.0):
         """from the next batch on, add every pair's field to the stream's (u,v) histogram (ofc_stream_set_histogram, the
@@ -84,6 +117,7 @@ class FlowStream:
         got = C.c_int()
         check(load().ofc_stream_finish(self._h, ptr(out), max(n, 1), C.byref(got)))
         self.pushed = 0
+        self._last_pairs = got.value
         return out[:got.value]
 
     def finish_clusters(self):
@@ -97,6 +131,7 @@ class FlowStream:
         got = C.c_int()
         check(load().ofc_stream_finish_clusters(self._h, ptr(out), ptr(counts), ptr(sums), max(n, 1), C.byref(got)))
         self.pushed = 0
+        self._last_pairs = got.value
         res = (out[:got.value], counts[:got.value])
         return res + (sums[:got.value],) if self.sums else res
 
