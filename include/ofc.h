@@ -582,6 +582,85 @@ int ofc_stream_read_camera(ofc_stream_t *s, double *models, int *status, int max
 int ofc_bench_motion(int device, const float *flow_dev, int W, int H, int npair, int what, int iters, float *ms_per_launch);
 
 /* ------------------------------------------------------------------------------------------
+ * Moving objects: connected components of a per-pixel key map, and one record per component.  Stands where the reference
+ * read YOLO boxes and segmented contours from files (KmeanGrids.py:16-50); neither is generated here.
+ * Definition (this text is the definition; every output is an integer, so any order of work gives equal bits).
+ * Key map: u8 [npair][H][W]; 255 = background.  It is the format ofc_kmeans_fit_dev leaves in labels_dev (0xFF =
+ * unassigned): a fitted clip's label buffer is a key map as it stands.
+ * Adjacency, within one pair only: connectivity 4 = pixels that share an edge, 8 = an edge or a corner.  Adjacent pixels
+ * p, q are connected iff key[p] == key[q] != 255.  A component is a class of the transitive closure.
+ * Root of a component: its smallest y*W + x.  Label map: int32 [npair][H][W], the root for a foreground pixel, -1 for
+ * background.  The root is a minimum, so the label map is unique whatever order the device works in.
+ * Record of a component, OFC_BLOB_FIELDS = 12 int64:
+ *   root, key, area, xmin, ymin, xmax, ymax, Sx, Sy, nvalid, Squ, Sqv
+ * (pixel count, inclusive bounding box, sums of x and of y over its pixels).  With a flow field [npair][H][W][2] f32 the last
+ * three cover the component's valid vectors: valid as the camera block has it (u, v finite and |u|, |v| < 1024), fixed point
+ * as there (qu = llrint((double)u * 65536)).  Without a field they are 0.  Sums, minima and maxima of integers only.
+ * Table of a pair: the records of its components with area >= min_area, ascending by root (raster order of first pixel).
+ * found[pair] = how many such components there are.  If found > max_blobs the pair delivers NO record (n = 0) and found
+ * stays exact: the overflow outcome is as deterministic as the rest.  The label map is complete whatever min_area and
+ * max_blobs are.
+ * Limits: W, H >= 1, W*H <= 2^31 - 1 (else OFC_EUNSUPPORTED); npair 1 .. 65535 (above: OFC_EUNSUPPORTED); connectivity 4
+ * or 8; min_area >= 1; max_blobs 1 .. 65536 (above: OFC_EUNSUPPORTED); everything else OFC_EINVAL.
+ * On the device: tiles of OFC_BLOB_TILE_W x OFC_BLOB_TILE_H pixels are resolved in LDS, then united across their borders
+ * by a minimum-index union-find (csrc/blobs.hip).  Every loop there is capped; a cap that is hit (it cannot be by the
+ * algorithm) makes the call return OFC_EHIP instead of hanging.
+ * ------------------------------------------------------------------------------------------ */
+#define OFC_BLOB_TILE_W 64
+#define OFC_BLOB_TILE_H 16
+#define OFC_BLOB_FIELDS 12
+/* Host only, no device is touched: OFC_OK iff the arguments are inside the limits above.  Every call below decides by it
+ * (with the values it does not take at their minimum) before anything is allocated or launched. */
+int ofc_blob_check(int W, int H, int npair, int connectivity, int min_area, int max_blobs);
+/* Key map from a field: flow_dev [npair][H][W][2] f32 (8-byte aligned) -> keys_dev u8 [npair][H][W].  Three stages:
+ * 1. use_thr != 0 (thr finite, >= 0): background unless u*u + v*v >= thr*thr, every operation rounded to f32 on its own:
+ *    the predicate of ofc_flow_weights_dev kind 1 (one shared device function); a NaN fails it.
+ * 2. k > 0 (k, mean, centers_c as for ofc_grid_assign_counts_dev): L = the byte ofc_lloyd_step_dev writes for the vector (the
+ *    shared device function); background unless bit L of `select` is set.
+ * 3. key = L, or 0 when merge != 0 or k == 0.
+ * k == 0: mean, centers_c, select are ignored.  k outside 0 .. 16: OFC_EUNSUPPORTED. */
+int ofc_blob_keys_dev(int device, const float *flow_dev, int W, int H, int npair, int use_thr, float thr, int k,
+                      const double *mean, const double *centers_c, uint32_t select, int merge, uint8_t *keys_dev);
+/* keys_dev -> labels_dev int32 [npair][H][W] (4-byte aligned), the label map above.  Returns when done. */
+int ofc_blob_label_dev(int device, const uint8_t *keys_dev, int W, int H, int npair, int connectivity, int32_t *labels_dev);
+/* keys_dev, its label map labels_dev and flow_dev (or NULL) -> table_dev int64 [npair][max_blobs][12] and found_dev int32
+ * [npair].  On the device a pair's first min(found, max_blobs) slots hold records in no specified order; slots past them
+ * are not written.  ofc_blob_table_read delivers the table defined above. */
+int ofc_blob_table_dev(int device, const uint8_t *keys_dev, const int32_t *labels_dev, const float *flow_dev, int W, int H,
+                       int npair, int min_area, int max_blobs, int64_t *table_dev, int32_t *found_dev);
+/* Device to host: table_host int64 [npair][max_blobs][12] receives each pair's records sorted by root in its first n_host
+ * [pair] rows (rows past them are zeroed), found_host [pair] the exact count; found > max_blobs gives n = 0. */
+int ofc_blob_table_read(int device, const int64_t *table_dev, const int32_t *found_dev, int npair, int max_blobs,
+                        int64_t *table_host, int32_t *n_host, int32_t *found_host);
+/* The whole chain on host buffers.  Exactly one of keys_host (u8 [npair][H][W]) and "flow_host plus the key parameters of
+ * ofc_blob_keys_dev" decides the key map: with keys_host the key parameters are ignored and flow_host (may be NULL) only
+ * feeds the records.  labels_host int32 [npair][H][W] and keys_out u8 [npair][H][W] may be NULL.  The rest as
+ * ofc_blob_table_read. */
+int ofc_blobs(int device, const uint8_t *keys_host, const float *flow_host, int W, int H, int npair, int use_thr, float thr,
+              int k, const double *mean, const double *centers_c, uint32_t select, int merge, int connectivity, int min_area,
+              int max_blobs, int32_t *labels_host, uint8_t *keys_out, int64_t *table_host, int32_t *n_host,
+              int32_t *found_host);
+/* A stream that finds moving objects: from the next batch on, every pair's field (the residual, when a camera is set) gets a
+ * key map, a label map and a table, on the compute stream behind everything else of the batch.  Foreground: u*u + v*v >= thr*thr
+ * (stage 1 of ofc_blob_keys_dev); with a model (ofc_stream_set_model, whenever it is set) the key is the model's label L of
+ * the vector, every label selected, nothing merged; without one the key is 0.  The records' sums come from the same field.
+ * connectivity 0 removes the blobs: the stream then launches exactly what a stream that never had them launches.  Same
+ * precondition as ofc_stream_set_camera (no frame and no undelivered result; otherwise OFC_EINVAL and nothing changes);
+ * connectivity, min_area, max_blobs as ofc_blob_check decides them for the stream's frame size, thr finite and >= 0. */
+int ofc_stream_set_blobs(ofc_stream_t *s, int connectivity, float thr, int min_area, int max_blobs);
+/* The tables of the n pairs the LAST finish delivered, as ofc_blob_table_read writes them: table_host [max_pairs][max_blobs]
+ * [12], n_host and found_host [max_pairs].  Valid under ofc_stream_read_camera's conditions: straight after a finish (either
+ * form) and until the next frame is pushed; max_pairs < n: OFC_EINVAL, nothing written; OFC_EINVAL without blobs. */
+int ofc_stream_read_blobs(ofc_stream_t *s, int64_t *table_host, int32_t *n_host, int32_t *found_host, int max_pairs);
+/* Measurement hook: average duration by HIP events of one stage over `iters` runs of the chain on keys_dev (flow_dev may be
+ * NULL unless what is 0), two warm-up runs before them; min_area 1, max_blobs 65536, buffers of the hook's own.  Every run
+ * executes the whole chain, so that each stage sees the state the stage before leaves; only the chosen part is timed.
+ * what = 0: the key kernel (threshold 0.5, no model) into a buffer of the hook's own; 1: the local stage; 2: the seam
+ * stage; 3: the flatten; 4: the label map (1 + 2 + 3); 5: the table (clear, areas, slots, records); 6: label map and table. */
+int ofc_bench_blobs(int device, const uint8_t *keys_dev, const float *flow_dev, int W, int H, int npair, int connectivity,
+                    int what, int iters, float *ms_per_run);
+
+/* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.
  * sims has n_large-n_small+1 entries; 0 where either norm is 0.  Integer-valued input (the hue columns) is summed exactly

@@ -16,6 +16,7 @@ UNIQUE_ID_BYTES = 128
 KPP_CHUNK = 1024          # OFC_KPP_CHUNK: samples per partial sum of the seeding's two-level cumulative sum
 UV_HIST_SHARE = 2048      # OFC_UV_HIST_SHARE: consecutive vectors a work-group of the histogram kernel takes at a time
 UV_HIST_MAX_GRID = 2048   # OFC_UV_HIST_MAX_GRID: most work-groups of one histogram launch
+BLOB_TILE_W, BLOB_TILE_H, BLOB_FIELDS = 64, 16, 12   # OFC_BLOB_TILE_W, OFC_BLOB_TILE_H, OFC_BLOB_FIELDS
 
 
 class OfcError(RuntimeError):
@@ -133,6 +134,15 @@ _PROTOS = {
     "ofc_stream_set_camera": ([_vp, _i, _vp, _i], _i),
     "ofc_stream_read_camera": ([_vp, _vp, _vp, _i], _i),
     "ofc_bench_motion": ([_i, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
+    "ofc_blob_check": ([_i, _i, _i, _i, _i, _i], _i),
+    "ofc_blob_keys_dev": ([_i, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, C.c_uint32, _i, _vp], _i),
+    "ofc_blob_label_dev": ([_i, _vp, _i, _i, _i, _i, _vp], _i),
+    "ofc_blob_table_dev": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "ofc_blob_table_read": ([_i, _vp, _vp, _i, _i, _vp, _vp, _vp], _i),
+    "ofc_blobs": ([_i, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, C.c_uint32, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "ofc_stream_set_blobs": ([_vp, _i, _f, _i, _i], _i),
+    "ofc_stream_read_blobs": ([_vp, _vp, _vp, _vp, _i], _i),
+    "ofc_bench_blobs": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

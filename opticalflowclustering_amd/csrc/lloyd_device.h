@@ -85,6 +85,18 @@ __device__ __forceinline__ int assign_point(const double (&x)[D], const double *
     return label;
 }
 
+// u*u + v*v with every product and the sum rounded to f32 on its own (numpy's f32 expression).  k_flow_weights takes its
+// square root (kind 0) or compares it with thr*thr (kind 1, "moving"); blobs.hip's key kernel makes the same comparison.
+__device__ __forceinline__ float flow_sq_mag(float u, float v)
+{
+#pragma clang fp contract(off)
+    const float uu = u * u, vv = v * v;
+    const float s = uu + vv;
+    return s;
+}
+// the "moving" predicate of ofc_flow_weights_dev kind 1: a NaN fails it
+__device__ __forceinline__ bool flow_is_moving(float u, float v, float thr2) { return flow_sq_mag(u, v) >= thr2; }
+
 // deterministic work-group sum of NV doubles per thread -> out[NV] (thread 0..NV-1 write)
 template <int NV>
 __device__ __forceinline__ void block_reduce_store(double (&v)[NV], double *lds /*[4][NV]*/, double *out)

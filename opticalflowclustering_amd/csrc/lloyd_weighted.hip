@@ -267,9 +267,7 @@ __global__ __launch_bounds__(256) void k_flow_weights(const float *__restrict__ 
 #pragma clang fp contract(off)
     typedef float v4f __attribute__((ext_vector_type(4)));
     auto one = [&](float u, float v) -> float {
-        const float uu = u * u, vv = v * v;
-        const float s = uu + vv;
-        return kind == 0 ? sqrtf(s) : (s >= thr2 ? 1.0f : 0.0f);
+        return kind == 0 ? sqrtf(flow_sq_mag(u, v)) : (flow_is_moving(u, v, thr2) ? 1.0f : 0.0f);
     };
     const int64_t n4 = n / 4;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {

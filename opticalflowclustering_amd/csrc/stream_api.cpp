@@ -5,7 +5,9 @@
 // cell means on the compute stream, while the field is still where the flow left it.  With a histogram
 // (ofc_stream_set_histogram) it is added to the stream's (u,v) table behind those, by uv_hist.hip's kernel.  With a camera
 // (ofc_stream_set_camera) every pair's camera motion is fitted and subtracted in place between the flow and the cell means
-// (motion_model.hip), so all of the above see the residual field.
+// (motion_model.hip), so all of the above see the residual field.  With blobs (ofc_stream_set_blobs) every pair's moving
+// regions are labelled and described behind all of those (blobs.hip), keyed by the model's label where there is a model.
+#include "blobs.h"
 #include "color_common.h"
 #include "lloyd_common.h"
 #include "motion_model.h"
@@ -46,6 +48,13 @@ struct ofc_stream {
     DevBuf cam_rec, cam_partial;       // MotionRec [max_pairs], grows with `cells`; the moment kernel's partials of a batch
     size_t cam_cap = 0;                // pairs
     int cam_pairs = 0;                 // pairs of the last finish: what ofc_stream_read_camera delivers
+    // the blobs, when there are any (blob_conn > 0): every pair's table, kept past the finish like the camera's fits
+    int blob_conn = 0, blob_min_area = 1, blob_max = 0;
+    float blob_thr = 0.f;
+    DevBuf blob_keys, blob_labels, blob_words, blob_err;   // one batch's key map, label map and area / slot words; the error word
+    DevBuf blob_table, blob_found;     // [max_pairs][blob_max][12] int64 and [max_pairs] int32: grow with `cells`
+    size_t blob_cap = 0;               // pairs
+    int blob_pairs = 0;                // pairs of the last finish: what ofc_stream_read_blobs delivers
 };
 
 namespace {
@@ -106,8 +115,30 @@ int ensure_camera(ofc_stream *s, int need_pairs)
     return OFC_OK;
 }
 
+// room for the blob tables of need_pairs pairs: same growth as ensure_camera, what was found so far is kept
+int ensure_blobs(ofc_stream *s, int need_pairs)
+{
+    if ((size_t)need_pairs <= s->blob_cap) return OFC_OK;
+    const size_t cap = std::max<size_t>(need_pairs, s->blob_cap ? s->blob_cap * 2 : 256);
+    const size_t per = sizeof(int64_t) * BLOB_NF * s->blob_max;
+    DevBuf nt, nf;
+    OFC_TRY(nt.alloc(cap * per));
+    OFC_TRY(nf.alloc(cap * sizeof(int32_t)));
+    if (s->blob_table.p && s->pairs_submitted) {
+        OFC_HIP(hipStreamSynchronize(s->compute));
+        OFC_HIP(hipMemcpy(nt.p, s->blob_table.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
+        OFC_HIP(hipMemcpy(nf.p, s->blob_found.p, (size_t)s->pairs_submitted * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    }
+    std::swap(s->blob_table.p, nt.p);
+    std::swap(s->blob_table.bytes, nt.bytes);
+    std::swap(s->blob_found.p, nf.p);
+    std::swap(s->blob_found.bytes, nf.bytes);
+    s->blob_cap = cap;
+    return OFC_OK;
+}
+
 // submit the frames packed in slot `i` (n >= 2): async upload, flow, with a camera its fit and subtraction, cell means,
-// with a model the cluster counts, and with a histogram the batch's share of the table
+// with a model the cluster counts, with a histogram the batch's share of the table, and with blobs the pairs' tables
 int submit(ofc_stream *s, int i)
 {
     ofc_stream::Slot &sl = s->slot[i];
@@ -116,6 +147,7 @@ int submit(ofc_stream *s, int i)
     OFC_TRY(ensure_cells(s, s->pairs_submitted + npair));
     if (s->k) OFC_TRY(ensure_clusters(s, s->pairs_submitted + npair));
     if (s->cam_kind) OFC_TRY(ensure_camera(s, s->pairs_submitted + npair));
+    if (s->blob_conn) OFC_TRY(ensure_blobs(s, s->pairs_submitted + npair));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
@@ -137,6 +169,21 @@ int submit(ofc_stream *s, int i)
     if (s->hist_bins)
         OFC_TRY(launch_uv_hist(sl.flows.as<float>(), (int64_t)P * npair, s->hist_bins, s->hist_range, s->hist.as<int64_t>(),
                                s->compute));
+    if (s->blob_conn) {
+        // moving pixels, keyed by the model's label where there is one: key map, label map, table, all of this batch
+        uint8_t *keys = s->blob_keys.as<uint8_t>();
+        int32_t *labels = s->blob_labels.as<int32_t>();
+        int *err = s->blob_err.as<int>();
+        OFC_TRY(launch_blob_keys(sl.flows.as<float>(), s->W, s->H, npair, true, s->blob_thr, s->k ? s->model.as<LloydState>() : nullptr,
+                                 s->k, (1u << s->k) - 1u, false, keys, s->compute));
+        OFC_TRY(launch_blob_local(keys, s->W, s->H, npair, s->blob_conn, labels, err, s->compute));
+        OFC_TRY(launch_blob_seam(keys, s->W, s->H, npair, s->blob_conn, labels, err, s->compute));
+        OFC_TRY(launch_blob_flatten(s->W, s->H, npair, labels, err, s->compute));
+        OFC_TRY(launch_blob_table(keys, labels, sl.flows.as<float>(), s->W, s->H, npair, s->blob_min_area, s->blob_max,
+                                  s->blob_words.as<int32_t>(),
+                                  s->blob_table.as<int64_t>() + (size_t)s->pairs_submitted * s->blob_max * BLOB_NF,
+                                  s->blob_found.as<int32_t>() + s->pairs_submitted, s->compute));
+    }
     OFC_HIP(hipEventRecord(sl.done, s->compute));
     sl.busy = true;
     sl.inflight_pairs = npair;
@@ -235,6 +282,7 @@ int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pai
                           hipMemcpyDeviceToHost));
     }
     s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
+    s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -284,6 +332,7 @@ int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts,
         if (sums) OFC_HIP(hipMemcpy(sums, s->sums.p, sizeof(double) * 2 * cells * s->k * n, hipMemcpyDeviceToHost));
     }
     s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
+    s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -372,6 +421,63 @@ int ofc_stream_read_camera(ofc_stream_t *s, double *models, int *status, int max
         if (status) status[i] = rec[i].status;
     }
     return OFC_OK;
+}
+
+int ofc_stream_set_blobs(ofc_stream_t *s, int connectivity, float thr, int min_area, int max_blobs)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (connectivity != 0) {
+        OFC_TRY(blob_check(s->W, s->H, s->batch, connectivity, min_area, max_blobs));
+        OFC_REQUIRE(std::isfinite(thr) && thr >= 0, "thr must be finite and >= 0");
+    }
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: set the blobs on a fresh stream or straight after a finish");
+    OFC_TRY(ensure_device(s->device));
+    s->blob_pairs = 0;
+    s->blob_table.release();               // the tables' layout may change: they are empty, start over
+    s->blob_found.release();
+    s->blob_cap = 0;
+    if (connectivity == 0) {
+        s->blob_keys.release();
+        s->blob_labels.release();
+        s->blob_words.release();
+        s->blob_err.release();
+        s->blob_conn = 0;
+        return OFC_OK;
+    }
+    const size_t n = (size_t)s->W * s->H * s->batch;
+    if (s->blob_keys.bytes < n) OFC_TRY(s->blob_keys.alloc(n));
+    if (s->blob_labels.bytes < n * sizeof(int32_t)) OFC_TRY(s->blob_labels.alloc(n * sizeof(int32_t)));
+    if (s->blob_words.bytes < n * sizeof(int32_t)) OFC_TRY(s->blob_words.alloc(n * sizeof(int32_t)));
+    if (s->blob_err.bytes < sizeof(int)) OFC_TRY(s->blob_err.alloc(sizeof(int)));
+    OFC_HIP(hipMemsetAsync(s->blob_err.p, 0, sizeof(int), s->compute));
+    OFC_HIP(hipStreamSynchronize(s->compute));
+    s->blob_conn = connectivity;
+    s->blob_thr = thr;
+    s->blob_min_area = min_area;
+    s->blob_max = max_blobs;
+    return OFC_OK;
+}
+
+int ofc_stream_read_blobs(ofc_stream_t *s, int64_t *table_host, int32_t *n_host, int32_t *found_host, int max_pairs)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->blob_conn > 0, "the stream has no blobs (ofc_stream_set_blobs)");
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: read the blobs straight after a finish");
+    OFC_REQUIRE(max_pairs >= s->blob_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->blob_pairs);
+    OFC_TRY(ensure_device(s->device));
+    if (!s->blob_pairs) return OFC_OK;
+    OFC_REQUIRE(table_host && n_host && found_host, "null pointer");
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    int e = 0;
+    OFC_HIP(hipMemcpy(&e, s->blob_err.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (e != 0) {
+        set_error("connected components: a capped loop ran out (stages %d); the tables are not valid", e);
+        return OFC_EHIP;
+    }
+    return blob_table_read(s->blob_table.as<int64_t>(), s->blob_found.as<int32_t>(), s->blob_pairs, s->blob_max, table_host, n_host,
+                           found_host);
 }
 
 void ofc_stream_destroy(ofc_stream_t *s)

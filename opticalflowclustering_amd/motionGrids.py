@@ -25,6 +25,12 @@ centres.  Vectors outside --hist-range take no part in the fit; their share is p
 With --camera translation|affine every pair's camera motion is fitted and removed on the device before anything else looks at
 the field (camera.py), on the resident route, on --stream and on --fit-stream: the clusters then describe the scene and not
 the camera, and --weights moving:0.5 means "moves against the background".  --camera-out writes the (pairs, 6) models.
+
+With --blobs FILE.csv every pair's moving objects are found on the device as well (blobs.py) and written one row per blob:
+pair, key, root x, root y, area, box, centroid, mean u, mean v.  A pixel is foreground when its vector's length reaches
+--blob-thr, and is keyed by its label against the centres (un-centred, as a stream labels), so neighbouring regions of
+different motion are different blobs; --blob-min-area drops small ones, --blob-connectivity is 4 or 8.  The same rows come
+out of the resident route, --stream and --fit-stream, with --camera after the camera is removed.
 """
 import argparse
 import os
@@ -64,6 +70,22 @@ def write_csv(path, rows):
         f.write(",".join(f"cell_{i}" for i in range(rows.shape[1])) + "\n")
         for r in rows:
             f.write(",".join(str(int(h)) for h in r) + "\n")
+
+
+MAX_BLOBS = 4096            # per pair; a pair with more delivers none (blobs.py), and its row count says so
+
+
+def write_blob_csv(path, blobs):
+    """blobs.CSV_HEADER, then one line per blob (blobs.Blobs.rows()), pairs in order and a pair's blobs by root"""
+    from .blobs import CSV_HEADER
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+        f.write(",".join(CSV_HEADER) + "\n")
+        for r in blobs.rows():
+            f.write(",".join(str(v) for v in r) + "\n")
+    over = [i for i, n in enumerate(blobs.found) if n > MAX_BLOBS]
+    if over:
+        print(f"blobs: {len(over)} pair(s) hold more than {MAX_BLOBS} components and deliver none (first: pair {over[0]})")
 
 
 def parse_weights(text):
@@ -124,10 +146,20 @@ def parse_arguments(argv=None):
     ap.add_argument("--camera-thresholds", type=parse_thresholds, default=(4.0, 2.0, 1.0), metavar="4,2,1",
                     help="inlier radii in px of the camera fit's re-selection rounds (the default is a guess, not tuned)")
     ap.add_argument("--camera-out", metavar="FILE.npy", help="write the (pairs, 6) camera models to this .npy file")
+    ap.add_argument("--blobs", metavar="FILE.csv", help="write one row per moving object (connected component) to this file")
+    ap.add_argument("--blob-thr", type=float, default=0.5, help="a pixel is foreground when its vector's length reaches this, px")
+    ap.add_argument("--blob-min-area", type=int, default=1, help="smallest component, in pixels, that becomes a row")
+    ap.add_argument("--blob-connectivity", type=int, choices=(4, 8), default=8)
     args = ap.parse_args(argv)
     if args.camera_out and args.camera == "none":
         ap.error("--camera-out needs --camera translation or --camera affine")
     args.camera_spec = None if args.camera == "none" else (args.camera, args.camera_thresholds)
+    if not (np.isfinite(args.blob_thr) and args.blob_thr >= 0):
+        ap.error("--blob-thr must be finite and >= 0")
+    if args.blob_min_area < 1:
+        ap.error("--blob-min-area must be at least 1")
+    args.blob_spec = dict(thr=args.blob_thr, connectivity=args.blob_connectivity, min_area=args.blob_min_area,
+                          max_blobs=MAX_BLOBS) if args.blobs else None
     if args.fit_stream:
         for flag, given in (("--model", args.model), ("--stream", args.stream), ("--weights", args.weights)):
             if given:
@@ -176,16 +208,16 @@ def read_gray_frames(path, device=0):
     return np.stack(frames)
 
 
-def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None):
+def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None, blobs=None, blobs_out=None):
     """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident; camera as
-    FlowStream's, its (pairs, 6) models saved to camera_out"""
+    FlowStream's, its (pairs, 6) models saved to camera_out; blobs as FlowStream's, their rows written to blobs_out"""
     from .stream import FlowStream
     fs, n = None, 0
     try:
         for gray in gray_frames(path, device):
             if fs is None:
                 fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, centers=centers,
-                                camera=camera)
+                                camera=camera, blobs=blobs)
             fs.push(gray)
             n += 1
         if n < 2:
@@ -193,6 +225,8 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
         counts = fs.finish_clusters()[1]
         if camera is not None and camera_out:
             np.save(camera_out, fs.camera_motion().params)
+        if blobs is not None and blobs_out:
+            write_blob_csv(blobs_out, fs.blobs())
         return counts
     finally:
         if fs is not None:
@@ -233,12 +267,12 @@ def main(argv=None):
         centers, _, _ = hist.fit(k, init="k-means++" if given is None else given, random_state=args.seed, n_init=args.n_init,
                                  device=args.device)
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out)
+                               args.camera_out, args.blob_spec, args.blobs)
         return _write_outputs(args, counts, centers)
     if args.stream:
         centers = given
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out)
+                               args.camera_out, args.blob_spec, args.blobs)
         return _write_outputs(args, counts, centers)
     from .pipeline import ClipPipeline
     frames = read_gray_frames(args.path, args.device)
@@ -262,6 +296,8 @@ def main(argv=None):
         else:
             centers, _, _ = pipe.run_kmeans("k-means++", k=k, random_state=args.seed)
         counts = pipe.cell_clusters(args.rows, args.cols)
+        if args.blob_spec:
+            write_blob_csv(args.blobs, pipe.blobs(by=centers, mean=None, labels=False, **args.blob_spec))
     finally:
         pipe.close()
     return _write_outputs(args, counts, centers)

@@ -254,6 +254,42 @@ class ClipPipeline:
         check(load().ofc_motion_subtract_dev(self.device, fp, self.W, self.H, n, _lib.ptr(params), fp))
         return cam.motion_from_history(params, status, moments, model)
 
+    def blobs(self, by="moving", thr=0.5, select=None, merge=False, connectivity=8, min_area=1, max_blobs=4096, labels=True,
+              mean="field"):
+        """the moving objects of every resident pair (blobs.py: connected components of a key map, one record each) ->
+        blobs.Blobs.  by='moving': the pixels whose vector's length reaches thr, all with key 0 (on hand-held footage call
+        compensate_camera first).  by='labels': the label buffer of the last run_kmeans() / assign() is the key map as it
+        stands; thr, select and merge do not apply.  by=centers ((k,2), a model fitted elsewhere): every vector is keyed by
+        the label assign(centers) would give it, centred by this field's own mean (mean='field'; mean=None labels un-centred,
+        as a FlowStream's model does, or pass the two values); select (labels to keep, None = all),
+        merge (join neighbouring regions of different labels) and thr (None: no motion test) as blobs.cluster_blobs.
+        The records' mean flow comes from the resident field.  Rank-local: a pair depends on itself alone."""
+        from . import blobs as bl
+        self.sync()
+        n, W, H = self.n_pairs, self.W, self.H
+        if isinstance(by, str) and by == "labels":
+            if self._label_k is None:
+                raise ValueError("blobs(by='labels') needs labels for the resident field: call run_kmeans() or assign() first "
+                                 "(run_flow() discards them)")
+            return bl.components_dev(self.labels.ptr, self.flows.ptr, W, H, n, connectivity, min_area, max_blobs, labels, self.device)
+        bl.check_args(W, H, n, connectivity, min_area, max_blobs)
+        keys = DeviceBuffer(n * W * H, self.device)
+        try:
+            if isinstance(by, str):
+                if by != "moving":
+                    raise ValueError(f"by should be 'moving', 'labels' or a (k,2) array of centres, got {by!r}")
+                bl.keys_dev(self.flows.ptr, W, H, n, keys.ptr, thr=thr, device=self.device)
+            else:
+                if isinstance(mean, str):
+                    _, mean, _ = self._centred_model(by)
+                bl.keys_dev(self.flows.ptr, W, H, n, keys.ptr, thr=thr, centers=by, mean=mean, select=select, merge=merge,
+                            device=self.device)
+            out = bl.components_dev(keys.ptr, self.flows.ptr, W, H, n, connectivity, min_area, max_blobs, labels, self.device)
+            out.keys = keys.download((n, H, W), np.uint8)
+            return out
+        finally:
+            keys.free()
+
     def sample_uv(self, idx):
         """host copy of a few (u,v) rows (for choosing the initial centres)"""
         out = np.empty((len(idx), 2), np.float32)

@@ -6,7 +6,8 @@ pair's field is labelled against the centres and counted per grid cell on the de
 (finish_clusters), so a fit can be deployed on footage that keeps arriving or is longer than memory.  With a histogram
 (histogram=(bins, range)) every pair's field is also added to the stream's (u,v) table (uvhist.py), so a model can be fitted
 on such footage too: histogram().fit(k).  With a camera (camera="affine") every pair's camera motion is fitted and subtracted
-on the device straight after the flow (camera.py), and all of the above see the residual field."""
+on the device straight after the flow (camera.py), and all of the above see the residual field.  With blobs
+(blobs=dict(thr=...)) every pair's moving regions are labelled and described on the device as well (blobs.py): blobs()."""
 import ctypes as C
 
 import numpy as np
@@ -16,7 +17,7 @@ from ._lib import FbParams, check, load, ptr
 
 class FlowStream:
     def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False,
-                 histogram=None, camera=None):
+                 histogram=None, camera=None, blobs=None):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
@@ -33,6 +34,35 @@ class FlowStream:
         self._last_pairs = 0                # pairs the last finish delivered
         if camera is not None:
             self.set_camera(camera)
+        self.blob_args = None               # (connectivity, thr, min_area, max_blobs) of the stream's blobs, or None
+        if blobs is not None:
+            self.set_blobs(**blobs)
+
+    def set_blobs(self, thr=0.5, connectivity=8, min_area=1, max_blobs=4096):
+        """from the next batch on, find every pair's moving objects (ofc_stream_set_blobs; blobs.py has the definition):
+        foreground where the vector's length reaches thr (of the residual field, with a camera), keyed by the model's
+        label where the stream has a model, so neighbouring regions of different motion stay apart; without one all keys
+        are 0.  connectivity=None or 0 removes them.  Only on a stream that holds no frame and no undelivered result, as
+        set_model; ValueError otherwise, and nothing changes."""
+        if not connectivity:
+            check(load().ofc_stream_set_blobs(self._h, 0, 0.0, 1, 1))
+            self.blob_args = None
+            return
+        args = (int(connectivity), float(thr), int(min_area), int(max_blobs))
+        check(load().ofc_stream_set_blobs(self._h, *args))
+        self.blob_args = args
+        self._last_pairs = 0
+
+    def blobs(self):
+        """-> blobs.Blobs (records and found; no label map) of the pairs the last finish() / finish_clusters() delivered
+        (ofc_stream_read_blobs).  Straight after a finish only; ValueError once frames are held again, and on a stream
+        without blobs."""
+        from .blobs import NF, Blobs, order_records
+        n, mb = self._last_pairs, self.blob_args[3] if self.blob_args else 1
+        table = np.zeros((max(n, 1), mb, NF), np.int64)
+        cnt, found = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        check(load().ofc_stream_read_blobs(self._h, ptr(table), ptr(cnt), ptr(found), max(n, 1)))
+        return Blobs(self.W, self.H, None, [order_records(table[i, :cnt[i]], int(cnt[i]), mb) for i in range(n)], found[:n])
 
     def set_camera(self, camera, thresholds=None):
         """from the next batch on, fit every pair's camera motion and subtract it in place before anything else looks at
