@@ -182,6 +182,7 @@ int ofc_bgr2gray(int device, const uint8_t *bgr, int W, int H, uint8_t *gray);
 /* cartToPolar + hue/normalize(MINMAX)/HSV2BGR (computeOpticalFlowModule.py:25-33) and
  * np.mean(magnitude) (computeOpticalFlow.py:114-117): flow HxWx2 f32 -> bgr HxWx3 u8 */
 int ofc_flow_to_bgr(int device, const float *flow, int W, int H, uint8_t *bgr, float *mean_mag);
+/* the same on n_frames resident fields; at most 65535 frames per call (OFC_EUNSUPPORTED, decided before any launch) */
 int ofc_flow_to_bgr_dev(int device, const float *flow_dev, int W, int H, int n_frames,
                         uint8_t *bgr_dev, float *mean_mag_dev);
 /* cvtColor(BGR2HSV) u8, H in [0,180) (KmeanGrids.py:86,336; color_kmeans.py:121) */
@@ -540,6 +541,12 @@ int ofc_bench_uv_hist(int device, const float *flow_dev, int64_t n, int bins, fl
 /* Host only, no device is touched: OFC_OK if fields of W x H can be fitted with `kind`.  OFC_EINVAL: kind not 1 or 2, W or
  * H < 1, kind 2 with W < 2 or H < 2.  OFC_EUNSUPPORTED: W * H * max(W, H) >= 2^37.  Every call below decides by it first. */
 int ofc_motion_check(int W, int H, int kind);
+/* Host only, no device is touched: how the moment kernel and the subtraction split npair fields of W x H.  A field is
+ * nshare = ceil(W H / 2048) shares of 2048 consecutive vectors; min(nshare, max(16, min(256, 2048 / npair))) work-groups
+ * per pair take `per` consecutive shares each.  out = { groups, per = ceil(nshare / groups), the groups that get at least
+ * one share, the shares of the last of those }.  The kernels and their launchers compute groups and per by the functions
+ * this reports.  OFC_EINVAL: out NULL, npair < 1, W or H < 1; OFC_EUNSUPPORTED as ofc_motion_check, or npair > 65535. */
+int ofc_motion_launch_geometry(int W, int H, int npair, int out[4]);
 /* Host only: the solve above on given moments.  p receives the model and *status 0, or zeros and *status 1 when the moments
  * cannot be solved.  OFC_EINVAL: a null pointer, kind not 1 or 2. */
 int ofc_motion_solve(const int64_t m[13], int kind, double p[6], int *status);
@@ -670,7 +677,8 @@ int ofc_bench_blobs(int device, const uint8_t *keys_dev, const float *flow_dev, 
 int ofc_sliding_cosine(int device, const double *small_v, int n_small, const double *large_v, int n_large,
                        double *sims);
 
-/* ---- synthetic input generator used by bench.py (not part of the reference path) ---- */
+/* ---- synthetic input generator used by bench.py (not part of the reference path) ----
+ * At most 65535 frames per call and 65535 rows per frame (OFC_EUNSUPPORTED, decided before any launch). */
 int ofc_synth_frames_dev(int device, uint8_t *frames_dev, int W, int H, int n_frames,
                          int t0, int seed);
 

@@ -125,6 +125,7 @@ _PROTOS = {
     "ofc_uv_hist": ([_i, _vp, _i64, _i, _f, _vp], _i),
     "ofc_bench_uv_hist": ([_i, _vp, _i64, _i, _f, _i, C.POINTER(_f)], _i),
     "ofc_motion_check": ([_i, _i, _i], _i),
+    "ofc_motion_launch_geometry": ([_i, _i, _i, _ip], _i),
     "ofc_motion_solve": ([_vp, _i, _vp, _ip], _i),
     "ofc_motion_moments_dev": ([_i, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "ofc_motion_fit_dev": ([_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp], _i),

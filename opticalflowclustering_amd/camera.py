@@ -57,6 +57,15 @@ def solve(moments, model="affine"):
     return p, st.value
 
 
+def motion_launch_geometry(W, H, npair=1):
+    """(groups, per, used, last): the work-groups per pair of the moment kernel and the subtraction over npair fields of
+    W x H, the 2048-vector shares each takes, the groups that get at least one share, and the shares of the last of those
+    (ofc_motion_launch_geometry); needs no device"""
+    out = (C.c_int * 4)()
+    check(load().ofc_motion_launch_geometry(W, H, npair, out))
+    return tuple(out)
+
+
 def motion_from_history(params, status, moments, model):
     """CameraMotion from a fit's outputs and its moment history (T+1, n, 13): the inliers are the n of the last round that
     solved, which the host solve decides as the device did"""

@@ -54,6 +54,10 @@ int ofc_flow_to_bgr_dev(int device, const float *flow_dev, int W, int H, int n_f
                         float *mean_mag_dev)
 {
     OFC_REQUIRE(flow_dev && bgr_dev && W >= 1 && H >= 1 && n_frames >= 1, "bad arguments");
+    if (n_frames > 65535) {                                // a frame is a row of the grid (gridDim.y)
+        set_error("n_frames = %d: at most 65535 frames per call", n_frames);
+        return OFC_EUNSUPPORTED;
+    }
     OFC_TRY(ensure_device(device));
     DevBuf partial, stats;
     OFC_TRY(partial.alloc(sizeof(double) * 3 * VIS_BLOCKS * (size_t)n_frames));
@@ -249,6 +253,10 @@ int ofc_sliding_cosine(int device, const double *small_v, int n_small, const dou
 int ofc_synth_frames_dev(int device, uint8_t *frames_dev, int W, int H, int n_frames, int t0, int seed)
 {
     OFC_REQUIRE(frames_dev && W >= 1 && H >= 1 && n_frames >= 1, "bad arguments");
+    if (n_frames > 65535 || H > 65535) {                   // frames are gridDim.z, rows gridDim.y
+        set_error("n_frames = %d, H = %d: at most 65535 frames per call and 65535 rows per frame", n_frames, H);
+        return OFC_EUNSUPPORTED;
+    }
     OFC_TRY(ensure_device(device));
     SynthParams sp;
     uint32_t st = 0x9E3779B9u * (uint32_t)(seed + 1);

@@ -81,6 +81,15 @@ extern "C" {
 
 int ofc_motion_check(int W, int H, int kind) { return motion_check(W, H, kind); }
 
+int ofc_motion_launch_geometry(int W, int H, int npair, int out[4])
+{
+    OFC_REQUIRE(out, "null pointer");
+    OFC_TRY(check_pairs(npair));
+    OFC_TRY(motion_check(W, H, 1));
+    motion_launch_geometry(W, H, npair, out);
+    return OFC_OK;
+}
+
 int ofc_motion_solve(const int64_t m[13], int kind, double p[6], int *status)
 {
     OFC_REQUIRE(m && p && status, "null pointer");

@@ -78,6 +78,18 @@ OFC_HD inline bool motion_solve(const int64_t *m, int kind, double *p)
     return true;
 }
 
+// Launch geometry of k_motion_moments and k_motion_subtract, in one place for the kernels, the launchers and
+// ofc_motion_launch_geometry: a pair's field is nshare shares of MOTION_SHARE vectors, `groups` work-groups per pair take
+// `per` consecutive shares each (the last used one what is left, the ones after it none).
+OFC_HD inline int motion_nshare(int W, int H) { return (int)(((int64_t)W * H + MOTION_SHARE - 1) / MOTION_SHARE); }
+OFC_HD inline int motion_per(int nshare, int groups) { return (nshare + groups - 1) / groups; }
+OFC_HD inline int motion_groups_of(int nshare, int npair)
+{
+    const int want = 2048 / (npair > 1 ? npair : 1);
+    const int capped = want < 256 ? want : 256, floored = capped > 16 ? capped : 16;
+    return nshare < floored ? nshare : floored;
+}
+
 // ---- motion_model.hip ----
 // OFC_OK, OFC_EINVAL or OFC_EUNSUPPORTED (message set): what ofc_motion_check documents.  Host only.
 int motion_check(int W, int H, int kind);
@@ -85,6 +97,8 @@ int motion_check(int W, int H, int kind);
 int motion_fit_check(int W, int H, int kind, const double *thresholds, int T);
 // work-groups per pair of the moment kernel, and so partial records per pair
 int motion_groups(int W, int H, int npair);
+// out = groups, per, the groups that get at least one share, the shares of the last of those.  Host only.
+void motion_launch_geometry(int W, int H, int npair, int out[4]);
 // one launch of the reduction: partial[npair][groups][13].  affine = false leaves the coordinate moments 0.
 int launch_motion_moments(const float *flow, int W, int H, int npair, const MotionRec *rec, int64_t *partial, bool affine,
                           hipStream_t s);

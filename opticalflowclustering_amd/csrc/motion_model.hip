@@ -70,7 +70,7 @@ __global__ __launch_bounds__(MM_THREADS) void k_motion_moments(const float2 *__r
     const int P = W * H;                                   // < 2^25 (motion_check)
     const float2 *f = flow + (size_t)pair * P;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nshare = (P + MOTION_SHARE - 1) / MOTION_SHARE, per = (nshare + gridDim.x - 1) / gridDim.x;
+    const int nshare = motion_nshare(W, H), per = motion_per(nshare, (int)gridDim.x);
     const int g1 = min(nshare, ((int)blockIdx.x + 1) * per);
     const int X0 = W - 1, Y0 = H - 1;
     const bool use = r.use != 0;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(MM_THREADS) void k_motion_subtract(const float2 *fl
     const float2 *f = flow + (size_t)pair * P;
     float2 *o = dst + (size_t)pair * P;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nshare = (P + MOTION_SHARE - 1) / MOTION_SHARE, per = (nshare + gridDim.x - 1) / gridDim.x;
+    const int nshare = motion_nshare(W, H), per = motion_per(nshare, (int)gridDim.x);
     const int g1 = min(nshare, ((int)blockIdx.x + 1) * per);
     const int X0 = W - 1, Y0 = H - 1;
     for (int g = blockIdx.x * per; g < g1; g++) {
@@ -240,8 +240,17 @@ int motion_fit_check(int W, int H, int kind, const double *thresholds, int T)
 
 int motion_groups(int W, int H, int npair)
 {
-    const int nshare = (int)(((int64_t)W * H + MOTION_SHARE - 1) / MOTION_SHARE);
-    return std::min(nshare, std::max(16, std::min(256, 2048 / std::max(npair, 1))));
+    return motion_groups_of(motion_nshare(W, H), npair);
+}
+
+void motion_launch_geometry(int W, int H, int npair, int out[4])
+{
+    const int nshare = motion_nshare(W, H), groups = motion_groups_of(nshare, npair), per = motion_per(nshare, groups);
+    const int used = (nshare + per - 1) / per;
+    out[0] = groups;
+    out[1] = per;
+    out[2] = used;
+    out[3] = nshare - (used - 1) * per;
 }
 
 int launch_motion_moments(const float *flow, int W, int H, int npair, const MotionRec *rec, int64_t *partial, bool affine,
