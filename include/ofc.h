@@ -667,6 +667,83 @@ int ofc_stream_read_blobs(ofc_stream_t *s, int64_t *table_host, int32_t *n_host,
 int ofc_bench_blobs(int device, const uint8_t *keys_dev, const float *flow_dev, int W, int H, int npair, int connectivity,
                     int what, int iters, float *ms_per_run);
 
+/* ---- Blob links: which blob of pair t continues as which blob of pair t+1.  The reference has no counterpart: it read
+ * boxes per frame from files (KmeanGrids.py:16-50) and never related one frame's boxes to the next's.
+ * Definition (normative, like the text above; every output is an integer).
+ * Moves: int32 [npair][H][W], one word per pixel, from a flow field f32 [npair][H][W][2].  A vector is valid exactly as the
+ * blob records and the camera block have it: u, v finite and |u|, |v| < 1024.  For a valid vector dx = u rounded to the
+ * nearest integer, ties to even, in f32 (__float2int_rn on the device, np.rint of the float32 on the host), dy the same
+ * from v; the word is (uint16)dy << 16 | (uint16)dx, and both fit int16 because |u| < 1024.  For an invalid vector the
+ * word is OFC_BLOB_NO_MOVE = 0x80008000 (dx = dy = -32768).  Moves are an object of their own, not read from the flow by the
+ * link kernel: the field the blobs are keyed on is often the residual after camera removal, while a pixel lands in the
+ * next frame by the WHOLE flow; take the moves before the camera is subtracted.
+ * Link votes: label maps `labels` int32 [npair][H][W] as ofc_blob_label_dev leaves them, the moves of the same pairs and
+ * min_area >= 1.  The area of a root is the number of pixels that carry it in its pair's label map.  For every transition
+ * t = 0 .. npair-2 and every pixel p = (x, y) of pair t with
+ *   a = labels[t][p], a >= 0 and area_t(a) >= min_area;  moves[t][p] != OFC_BLOB_NO_MOVE;
+ *   x' = x + dx, y' = y + dy, 0 <= x' < W and 0 <= y' < H;
+ *   b = labels[t+1][y'*W + x'], b >= 0 and area_t+1(b) >= min_area
+ * the pixel is one vote for (a, b).  (A label outside [-1, W*H) in a caller's map votes for nothing and is never used as
+ * an index.)
+ * Link table of transition t: one row root_a, root_b, votes (OFC_BLOB_LINK_FIELDS = 3 int64) per distinct (a, b) with at
+ * least one vote, ascending by (root_a, root_b).  nlinks[t] = the number of rows when that is <= max_links; otherwise the
+ * transition delivers NO row and nlinks[t] = -1.  Overflow happens if and only if there are more than max_links distinct
+ * links, so the outcome is as deterministic as the rest.  npair = 1 is allowed and has zero transitions.
+ * Limits: those of ofc_blob_check, plus max_links 1 .. 65536 (above: OFC_EUNSUPPORTED; below 1: OFC_EINVAL).
+ * On the device a transition's table is open addressing on the 64-bit key (a << 32) | b; every probe loop is capped at the
+ * table's capacity, and a cap that is hit with room left (it cannot be by the algorithm) makes ofc_blob_links_read return
+ * OFC_EHIP. ---- */
+#define OFC_BLOB_LINK_FIELDS 3
+#define OFC_BLOB_NO_MOVE 0x80008000u
+/* Host only, no device is touched: OFC_OK iff the arguments are inside the limits above.  Every call below decides by it
+ * (with the values it does not take at their minimum) before anything is allocated or launched.  No counterpart in the
+ * reference (it read boxes from files), as for every call of this block. */
+int ofc_blob_link_check(int W, int H, int npair, int min_area, int max_links);
+/* Host only: the bytes links_dev needs for ntrans transitions under max_links, 0 for arguments outside the limits.  Layout
+ * (private to the library but stable within a build): uint64 keys [ntrans][cap], then int32 votes [ntrans][cap], with cap the
+ * smallest power of two >= 2 * max_links; the counter words are nlinks_dev.  No counterpart in the reference. */
+size_t ofc_blob_links_bytes(int max_links, int ntrans);
+/* flow_dev [npair][H][W][2] f32 (8-byte aligned) -> moves_dev int32 [npair][H][W] (4-byte aligned; 16-byte loads and stores
+ * where both bases allow).  Returns when done.  No counterpart in the reference. */
+int ofc_blob_moves_dev(int device, const float *flow_dev, int W, int H, int npair, int32_t *moves_dev);
+/* labels_dev, moves_dev int32 [npair][H][W] -> the npair-1 transitions' tables in links_dev (8-byte aligned,
+ * ofc_blob_links_bytes(max_links, npair - 1) bytes) and their counter words in nlinks_dev int32 [npair-1], both as
+ * ofc_blob_links_read interprets them.  The areas are counted again from the label maps into scratch of the library's own.
+ * Neither input is written.  npair = 1: nothing is launched and neither output is touched (both may be NULL).  Returns when
+ * done.  No counterpart in the reference. */
+int ofc_blob_links_dev(int device, const int32_t *labels_dev, const int32_t *moves_dev, int W, int H, int npair, int min_area,
+                       int max_links, void *links_dev, int32_t *nlinks_dev);
+/* Device to host: links_host int64 [ntrans][max_links][3] receives each transition's rows sorted by (root_a, root_b) in its
+ * first nlinks_host[t] rows, rows past them zeroed; an overflowed transition has nlinks_host[t] = -1 and all its rows
+ * zeroed.  ntrans = 0 writes nothing.  No counterpart in the reference. */
+int ofc_blob_links_read(int device, const void *links_dev, const int32_t *nlinks_dev, int ntrans, int max_links,
+                        int64_t *links_host, int32_t *nlinks_host);
+/* The whole chain on host buffers: labels_host int32 [npair][H][W] (ofc_blobs' labels_host) and flow_host f32 [npair][H][W][2],
+ * the field that says where pixels go (before any camera removal) -> moves_out int32 [npair][H][W] (may be NULL), links_host
+ * and nlinks_host as ofc_blob_links_read writes them for npair - 1 transitions.  No counterpart in the reference. */
+int ofc_blob_links(int device, const int32_t *labels_host, const float *flow_host, int W, int H, int npair, int min_area,
+                   int max_links, int32_t *moves_out, int64_t *links_host, int32_t *nlinks_host);
+/* A stream with blobs (ofc_stream_set_blobs; without them OFC_EINVAL) that also links them: from the next batch on the
+ * batch's moves are taken from the field BEFORE the camera (if any) is subtracted, and behind the batch's label maps every
+ * transition is voted: those inside the batch, and the one from the previous batch's last pair, whose label map, moves and
+ * areas the stream carries over (12 bytes per pixel).  A finish ends the clip: the first pair after it has no predecessor.
+ * min_area is the stream's blobs' own.  max_links 0 removes the links: the stream then launches exactly what a stream with
+ * blobs alone launches; ofc_stream_set_blobs with connectivity 0 removes them too.  Same precondition as
+ * ofc_stream_set_blobs (no frame and no undelivered result; otherwise OFC_EINVAL and nothing changes); like it, it empties
+ * what ofc_stream_read_blobs delivers.  max_links as ofc_blob_link_check decides it.  No counterpart in the reference. */
+int ofc_stream_set_blob_links(ofc_stream_t *s, int max_links);
+/* The n - 1 transitions of the n pairs the LAST finish delivered, as ofc_blob_links_read writes them: links_host
+ * [max_trans][max_links][3], nlinks_host [max_trans].  Valid under ofc_stream_read_blobs' conditions; max_trans < n - 1:
+ * OFC_EINVAL, nothing written; OFC_EINVAL without links.  No counterpart in the reference. */
+int ofc_stream_read_blob_links(ofc_stream_t *s, int64_t *links_host, int32_t *nlinks_host, int max_trans);
+/* Measurement hook: average duration by HIP events of one part over `iters` runs of the chain moves, areas, clears, votes on
+ * labels_dev and flow_dev, two warm-up runs before them; min_area 1, max_links 65536, buffers of the hook's own.  Every run
+ * executes the whole chain; only the chosen part is timed.  what = 0: the moves kernel; 1: the areas (clear and sweep);
+ * 2: the link kernel with the clears of its tables; 3: all of it.  npair = 1 has no transition: 2 times two event records.
+ * No counterpart in the reference. */
+int ofc_bench_blob_links(int device, const int32_t *labels_dev, const float *flow_dev, int W, int H, int npair, int what,
+                         int iters, float *ms_per_run);
+
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.

@@ -17,6 +17,7 @@ KPP_CHUNK = 1024          # OFC_KPP_CHUNK: samples per partial sum of the seedin
 UV_HIST_SHARE = 2048      # OFC_UV_HIST_SHARE: consecutive vectors a work-group of the histogram kernel takes at a time
 UV_HIST_MAX_GRID = 2048   # OFC_UV_HIST_MAX_GRID: most work-groups of one histogram launch
 BLOB_TILE_W, BLOB_TILE_H, BLOB_FIELDS = 64, 16, 12   # OFC_BLOB_TILE_W, OFC_BLOB_TILE_H, OFC_BLOB_FIELDS
+BLOB_LINK_FIELDS, BLOB_NO_MOVE = 3, -0x7fff8000      # OFC_BLOB_LINK_FIELDS; OFC_BLOB_NO_MOVE (0x80008000) as an int32
 
 
 class OfcError(RuntimeError):
@@ -144,6 +145,15 @@ _PROTOS = {
     "ofc_stream_set_blobs": ([_vp, _i, _f, _i, _i], _i),
     "ofc_stream_read_blobs": ([_vp, _vp, _vp, _vp, _i], _i),
     "ofc_bench_blobs": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
+    "ofc_blob_link_check": ([_i, _i, _i, _i, _i], _i),
+    "ofc_blob_links_bytes": ([_i, _i], _sz),
+    "ofc_blob_moves_dev": ([_i, _vp, _i, _i, _i, _vp], _i),
+    "ofc_blob_links_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "ofc_blob_links_read": ([_i, _vp, _vp, _i, _i, _vp, _vp], _i),
+    "ofc_blob_links": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "ofc_stream_set_blob_links": ([_vp, _i], _i),
+    "ofc_stream_read_blob_links": ([_vp, _vp, _vp, _i], _i),
+    "ofc_bench_blob_links": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

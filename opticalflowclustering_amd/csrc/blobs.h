@@ -28,6 +28,9 @@ int launch_blob_flatten(int W, int H, int npair, int32_t *labels, int *err, hipS
 // clears words and found, counts, hands out slots, accumulates.  flow may be nullptr.
 int launch_blob_table(const uint8_t *keys, const int32_t *labels, const float *flow, int W, int H, int npair, int min_area,
                       int max_blobs, int32_t *words, int64_t *table, int32_t *found, hipStream_t s);
+// labels [npair][H][W] -> words int32 [npair][H][W]: cleared, then the pixel count of every component at its root (the
+// first step of launch_blob_table, on its own for the blob links)
+int launch_blob_area(const int32_t *labels, int W, int H, int npair, int32_t *words, hipStream_t s);
 
 // slots in the device's order -> the table of the definition: sorted by root, none on overflow
 inline void blob_order_records(const int64_t *slots, int found, int max_blobs, int64_t *out, int32_t *n)

@@ -579,6 +579,15 @@ int launch_blob_flatten(int W, int H, int npair, int32_t *labels, int *err, hipS
     return OFC_OK;
 }
 
+int launch_blob_area(const int32_t *labels, int W, int H, int npair, int32_t *words, hipStream_t s)
+{
+    const int P = W * H;
+    OFC_HIP(hipMemsetAsync(words, 0, sizeof(int32_t) * (size_t)P * npair, s));
+    hipLaunchKernelGGL(k_blob_area, dim3((unsigned)cdiv64(P, BLOB_SHARE), npair), dim3(BL_THREADS), 0, s, labels, P, words);
+    OFC_HIP(hipGetLastError());
+    return OFC_OK;
+}
+
 int launch_blob_table(const uint8_t *keys, const int32_t *labels, const float *flow, int W, int H, int npair, int min_area,
                       int max_blobs, int32_t *words, int64_t *table, int32_t *found, hipStream_t s)
 {

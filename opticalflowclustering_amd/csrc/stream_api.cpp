@@ -7,7 +7,10 @@
 // (ofc_stream_set_camera) every pair's camera motion is fitted and subtracted in place between the flow and the cell means
 // (motion_model.hip), so all of the above see the residual field.  With blobs (ofc_stream_set_blobs) every pair's moving
 // regions are labelled and described behind all of those (blobs.hip), keyed by the model's label where there is a model.
-#include "blobs.h"
+// With blob links (ofc_stream_set_blob_links) the batch's moves are taken from the field before the camera is subtracted,
+// and behind the blobs every transition between consecutive pairs is voted (blob_links.hip): those inside the batch, and
+// the one from the previous batch's last pair, whose label map, moves and areas the stream carries over.
+#include "blob_links.h"
 #include "color_common.h"
 #include "lloyd_common.h"
 #include "motion_model.h"
@@ -55,6 +58,12 @@ struct ofc_stream {
     DevBuf blob_table, blob_found;     // [max_pairs][blob_max][12] int64 and [max_pairs] int32: grow with `cells`
     size_t blob_cap = 0;               // pairs
     int blob_pairs = 0;                // pairs of the last finish: what ofc_stream_read_blobs delivers
+    // the blob links, when there are any (link_max > 0; only with blobs): transition g leads from pair g to pair g + 1 of the clip
+    int link_max = 0;
+    DevBuf link_moves, link_areas;     // one batch's moves and areas at the roots, int32 [batch][H][W] each
+    DevBuf link_carry;                 // the previous batch's last pair: label map, moves, areas, int32 [3][H][W]
+    DevBuf link_keys, link_votes, link_counters;   // [max_pairs][cap] uint64, [max_pairs][cap] int32, [max_pairs] int32: grow
+    size_t link_cap = 0;               // transitions
 };
 
 namespace {
@@ -137,6 +146,58 @@ int ensure_blobs(ofc_stream *s, int need_pairs)
     return OFC_OK;
 }
 
+// room for the link tables of need_pairs pairs (one transition fewer, never more): same growth as ensure_blobs, what was
+// voted so far is kept
+int ensure_links(ofc_stream *s, int need_pairs)
+{
+    if ((size_t)need_pairs <= s->link_cap) return OFC_OK;
+    const size_t cap = std::max<size_t>(need_pairs, s->link_cap ? s->link_cap * 2 : 256);
+    const size_t slots = blob_link_capacity(s->link_max);
+    DevBuf nk, nv, nc;
+    OFC_TRY(nk.alloc(cap * slots * sizeof(uint64_t)));
+    OFC_TRY(nv.alloc(cap * slots * sizeof(int32_t)));
+    OFC_TRY(nc.alloc(cap * sizeof(int32_t)));
+    if (s->link_keys.p && s->pairs_submitted) {
+        const size_t have = (size_t)s->pairs_submitted;
+        OFC_HIP(hipStreamSynchronize(s->compute));
+        OFC_HIP(hipMemcpy(nk.p, s->link_keys.p, have * slots * sizeof(uint64_t), hipMemcpyDeviceToDevice));
+        OFC_HIP(hipMemcpy(nv.p, s->link_votes.p, have * slots * sizeof(int32_t), hipMemcpyDeviceToDevice));
+        OFC_HIP(hipMemcpy(nc.p, s->link_counters.p, have * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    }
+    std::swap(s->link_keys.p, nk.p);
+    std::swap(s->link_keys.bytes, nk.bytes);
+    std::swap(s->link_votes.p, nv.p);
+    std::swap(s->link_votes.bytes, nv.bytes);
+    std::swap(s->link_counters.p, nc.p);
+    std::swap(s->link_counters.bytes, nc.bytes);
+    s->link_cap = cap;
+    return OFC_OK;
+}
+
+// Behind a batch's label maps: its areas, then the votes of the transition from the carried pair (when the clip has one
+// before this batch) and of the batch's inner transitions; then the batch's last pair becomes the carried one.
+int submit_links(ofc_stream *s, const int32_t *labels, int npair)
+{
+    const size_t P = (size_t)s->W * s->H, slots = blob_link_capacity(s->link_max);
+    const int base = s->pairs_submitted, first = base > 0 ? base - 1 : 0, ntrans = base + npair - 1 - first;
+    const int32_t *moves = s->link_moves.as<int32_t>();
+    int32_t *areas = s->link_areas.as<int32_t>(), *carry = s->link_carry.as<int32_t>();
+    uint64_t *keys = s->link_keys.as<uint64_t>();
+    int32_t *votes = s->link_votes.as<int32_t>(), *counters = s->link_counters.as<int32_t>();
+    OFC_TRY(launch_blob_area(labels, s->W, s->H, npair, areas, s->compute));
+    OFC_TRY(launch_blob_links_clear(s->link_max, ntrans, keys + first * slots, votes + first * slots, counters + first, s->compute));
+    if (base > 0)
+        OFC_TRY(launch_blob_links(carry, carry + P, carry + 2 * P, labels, areas, s->W, s->H, 1, s->blob_min_area, s->link_max,
+                                  keys + first * slots, votes + first * slots, counters + first, s->compute));
+    OFC_TRY(launch_blob_links(labels, moves, areas, labels + P, areas + P, s->W, s->H, npair - 1, s->blob_min_area, s->link_max,
+                              keys + (size_t)base * slots, votes + (size_t)base * slots, counters + base, s->compute));
+    const size_t last = (size_t)(npair - 1) * P, bytes = sizeof(int32_t) * P;
+    OFC_HIP(hipMemcpyAsync(carry, labels + last, bytes, hipMemcpyDeviceToDevice, s->compute));
+    OFC_HIP(hipMemcpyAsync(carry + P, moves + last, bytes, hipMemcpyDeviceToDevice, s->compute));
+    OFC_HIP(hipMemcpyAsync(carry + 2 * P, areas + last, bytes, hipMemcpyDeviceToDevice, s->compute));
+    return OFC_OK;
+}
+
 // submit the frames packed in slot `i` (n >= 2): async upload, flow, with a camera its fit and subtraction, cell means,
 // with a model the cluster counts, with a histogram the batch's share of the table, and with blobs the pairs' tables
 int submit(ofc_stream *s, int i)
@@ -148,10 +209,13 @@ int submit(ofc_stream *s, int i)
     if (s->k) OFC_TRY(ensure_clusters(s, s->pairs_submitted + npair));
     if (s->cam_kind) OFC_TRY(ensure_camera(s, s->pairs_submitted + npair));
     if (s->blob_conn) OFC_TRY(ensure_blobs(s, s->pairs_submitted + npair));
+    if (s->link_max) OFC_TRY(ensure_links(s, s->pairs_submitted + npair));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
     OFC_TRY(ofc_flow_calc_frames_dev(s->flow, sl.frames.as<uint8_t>(), sl.n_frames, sl.flows.as<float>()));
+    // where the pixels go is what the whole flow says: the moves are taken before the camera is subtracted
+    if (s->link_max) OFC_TRY(launch_blob_moves(sl.flows.as<float>(), s->W, s->H, npair, s->link_moves.as<int32_t>(), s->compute));
     if (s->cam_kind) {
         MotionRec *rec = s->cam_rec.as<MotionRec>() + s->pairs_submitted;
         OFC_TRY(motion_fit_async(sl.flows.as<float>(), s->W, s->H, npair, s->cam_kind, s->cam_thr, s->cam_T, rec,
@@ -183,6 +247,7 @@ int submit(ofc_stream *s, int i)
                                   s->blob_words.as<int32_t>(),
                                   s->blob_table.as<int64_t>() + (size_t)s->pairs_submitted * s->blob_max * BLOB_NF,
                                   s->blob_found.as<int32_t>() + s->pairs_submitted, s->compute));
+        if (s->link_max) OFC_TRY(submit_links(s, labels, npair));
     }
     OFC_HIP(hipEventRecord(sl.done, s->compute));
     sl.busy = true;
@@ -423,6 +488,13 @@ int ofc_stream_read_camera(ofc_stream_t *s, double *models, int *status, int max
     return OFC_OK;
 }
 
+static void release_links(ofc_stream *s)
+{
+    for (DevBuf *b : {&s->link_moves, &s->link_areas, &s->link_carry, &s->link_keys, &s->link_votes, &s->link_counters}) b->release();
+    s->link_cap = 0;
+    s->link_max = 0;
+}
+
 int ofc_stream_set_blobs(ofc_stream_t *s, int connectivity, float thr, int min_area, int max_blobs)
 {
     OFC_REQUIRE(s, "null pointer");
@@ -443,6 +515,7 @@ int ofc_stream_set_blobs(ofc_stream_t *s, int connectivity, float thr, int min_a
         s->blob_words.release();
         s->blob_err.release();
         s->blob_conn = 0;
+        release_links(s);
         return OFC_OK;
     }
     const size_t n = (size_t)s->W * s->H * s->batch;
@@ -478,6 +551,41 @@ int ofc_stream_read_blobs(ofc_stream_t *s, int64_t *table_host, int32_t *n_host,
     }
     return blob_table_read(s->blob_table.as<int64_t>(), s->blob_found.as<int32_t>(), s->blob_pairs, s->blob_max, table_host, n_host,
                            found_host);
+}
+
+int ofc_stream_set_blob_links(ofc_stream_t *s, int max_links)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->blob_conn > 0, "the stream has no blobs (ofc_stream_set_blobs): there is nothing to link");
+    if (max_links != 0) OFC_TRY(blob_link_check(s->W, s->H, s->batch, s->blob_min_area, max_links));
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: set the links on a fresh stream or straight after a finish");
+    OFC_TRY(ensure_device(s->device));
+    release_links(s);                      // the tables' layout may change: they are empty, start over
+    s->blob_pairs = 0;                     // ... and so are the blob tables, as after ofc_stream_set_blobs
+    if (max_links == 0) return OFC_OK;
+    const size_t P = (size_t)s->W * s->H;
+    OFC_TRY(s->link_moves.alloc(sizeof(int32_t) * P * s->batch));
+    OFC_TRY(s->link_areas.alloc(sizeof(int32_t) * P * s->batch));
+    OFC_TRY(s->link_carry.alloc(sizeof(int32_t) * P * 3));
+    s->link_max = max_links;
+    return OFC_OK;
+}
+
+int ofc_stream_read_blob_links(ofc_stream_t *s, int64_t *links_host, int32_t *nlinks_host, int max_trans)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->link_max > 0, "the stream has no blob links (ofc_stream_set_blob_links)");
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: read the links straight after a finish");
+    const int ntrans = s->blob_pairs > 0 ? s->blob_pairs - 1 : 0;
+    OFC_REQUIRE(max_trans >= ntrans, "the outputs hold %d transitions, the last finish delivered %d", max_trans, ntrans);
+    OFC_TRY(ensure_device(s->device));
+    if (!ntrans) return OFC_OK;
+    OFC_REQUIRE(links_host && nlinks_host, "null pointer");
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    return blob_links_read(s->link_keys.as<uint64_t>(), s->link_votes.as<int32_t>(), s->link_counters.as<int32_t>(), ntrans,
+                           s->link_max, links_host, nlinks_host);
 }
 
 void ofc_stream_destroy(ofc_stream_t *s)

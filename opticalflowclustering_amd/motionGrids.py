@@ -31,6 +31,9 @@ pair, key, root x, root y, area, box, centroid, mean u, mean v.  A pixel is fore
 --blob-thr, and is keyed by its label against the centres (un-centred, as a stream labels), so neighbouring regions of
 different motion are different blobs; --blob-min-area drops small ones, --blob-connectivity is 4 or 8.  The same rows come
 out of the resident route, --stream and --fit-stream, with --camera after the camera is removed.
+With --tracks (it needs --blobs) the blobs of consecutive pairs are linked on the device as well (blobs.link: a blob's pixels
+land, by their own flow vectors before the camera is removed, on the next pair's blobs) and every row gets a last column,
+the id of the track its blob belongs to (blobs.tracks).
 """
 import argparse
 import os
@@ -73,16 +76,22 @@ def write_csv(path, rows):
 
 
 MAX_BLOBS = 4096            # per pair; a pair with more delivers none (blobs.py), and its row count says so
+MAX_LINKS = 4096            # per transition, with --tracks; a transition with more delivers none and breaks every track
 
 
-def write_blob_csv(path, blobs):
-    """blobs.CSV_HEADER, then one line per blob (blobs.Blobs.rows()), pairs in order and a pair's blobs by root"""
-    from .blobs import CSV_HEADER
+def write_blob_csv(path, blobs, tracks=False):
+    """blobs.CSV_HEADER, then one line per blob (blobs.Blobs.rows()), pairs in order and a pair's blobs by root; with
+    tracks (the Blobs then carries links) blobs.TRACK_CSV_HEADER and the track id as a last column"""
+    from .blobs import CSV_HEADER, TRACK_CSV_HEADER
+    from .blobs import tracks as find_tracks
+    found = find_tracks(blobs) if tracks else None
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "w", newline="") as f:
-        f.write(",".join(CSV_HEADER) + "\n")
-        for r in blobs.rows():
+        f.write(",".join(TRACK_CSV_HEADER if tracks else CSV_HEADER) + "\n")
+        for r in blobs.rows(found):
             f.write(",".join(str(v) for v in r) + "\n")
+    if found is not None and found.broken:
+        print(f"tracks: {len(found.broken)} transition(s) broke every track through them (first: {found.broken[0]})")
     over = [i for i, n in enumerate(blobs.found) if n > MAX_BLOBS]
     if over:
         print(f"blobs: {len(over)} pair(s) hold more than {MAX_BLOBS} components and deliver none (first: pair {over[0]})")
@@ -150,6 +159,8 @@ def parse_arguments(argv=None):
     ap.add_argument("--blob-thr", type=float, default=0.5, help="a pixel is foreground when its vector's length reaches this, px")
     ap.add_argument("--blob-min-area", type=int, default=1, help="smallest component, in pixels, that becomes a row")
     ap.add_argument("--blob-connectivity", type=int, choices=(4, 8), default=8)
+    ap.add_argument("--tracks", action="store_true",
+                    help="link the blobs of consecutive pairs and add a track id as the last column of the --blobs file")
     args = ap.parse_args(argv)
     if args.camera_out and args.camera == "none":
         ap.error("--camera-out needs --camera translation or --camera affine")
@@ -160,6 +171,9 @@ def parse_arguments(argv=None):
         ap.error("--blob-min-area must be at least 1")
     args.blob_spec = dict(thr=args.blob_thr, connectivity=args.blob_connectivity, min_area=args.blob_min_area,
                           max_blobs=MAX_BLOBS) if args.blobs else None
+    if args.tracks and not args.blobs:
+        ap.error("--tracks adds a column to the --blobs file: it needs --blobs FILE.csv")
+    args.max_links = MAX_LINKS if args.tracks else 0
     if args.fit_stream:
         for flag, given in (("--model", args.model), ("--stream", args.stream), ("--weights", args.weights)):
             if given:
@@ -208,11 +222,15 @@ def read_gray_frames(path, device=0):
     return np.stack(frames)
 
 
-def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None, blobs=None, blobs_out=None):
+def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None, blobs=None, blobs_out=None,
+                  max_links=0):
     """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident; camera as
-    FlowStream's, its (pairs, 6) models saved to camera_out; blobs as FlowStream's, their rows written to blobs_out"""
+    FlowStream's, its (pairs, 6) models saved to camera_out; blobs as FlowStream's, their rows written to blobs_out, with
+    max_links linked and with their track ids"""
     from .stream import FlowStream
     fs, n = None, 0
+    if blobs is not None and max_links:
+        blobs = dict(blobs, max_links=max_links)
     try:
         for gray in gray_frames(path, device):
             if fs is None:
@@ -226,7 +244,7 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
         if camera is not None and camera_out:
             np.save(camera_out, fs.camera_motion().params)
         if blobs is not None and blobs_out:
-            write_blob_csv(blobs_out, fs.blobs())
+            write_blob_csv(blobs_out, fs.blobs(), tracks=bool(max_links))
         return counts
     finally:
         if fs is not None:
@@ -267,12 +285,12 @@ def main(argv=None):
         centers, _, _ = hist.fit(k, init="k-means++" if given is None else given, random_state=args.seed, n_init=args.n_init,
                                  device=args.device)
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out, args.blob_spec, args.blobs)
+                               args.camera_out, args.blob_spec, args.blobs, args.max_links)
         return _write_outputs(args, counts, centers)
     if args.stream:
         centers = given
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out, args.blob_spec, args.blobs)
+                               args.camera_out, args.blob_spec, args.blobs, args.max_links)
         return _write_outputs(args, counts, centers)
     from .pipeline import ClipPipeline
     frames = read_gray_frames(args.path, args.device)
@@ -282,6 +300,8 @@ def main(argv=None):
         pipe.upload_frames(frames)
         pipe.run_flow()
         if args.camera_spec:
+            if args.max_links:
+                pipe.capture_moves()            # where the pixels go: before the camera is taken out of the field
             motion = pipe.compensate_camera(*args.camera_spec)
             if args.camera_out:
                 np.save(args.camera_out, motion.params)
@@ -297,7 +317,8 @@ def main(argv=None):
             centers, _, _ = pipe.run_kmeans("k-means++", k=k, random_state=args.seed)
         counts = pipe.cell_clusters(args.rows, args.cols)
         if args.blob_spec:
-            write_blob_csv(args.blobs, pipe.blobs(by=centers, mean=None, labels=False, **args.blob_spec))
+            write_blob_csv(args.blobs, pipe.blobs(by=centers, mean=None, labels=False, links=args.max_links or None, **args.blob_spec),
+                           tracks=bool(args.max_links))
     finally:
         pipe.close()
     return _write_outputs(args, counts, centers)

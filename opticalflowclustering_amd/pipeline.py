@@ -56,6 +56,8 @@ class ClipPipeline:
         self._sums_valid = False
         self.weights = None                 # N f32 sample weights for run_kmeans, allocated on first use
         self._label_k = None                # the k the resident labels were written with (run_kmeans / assign), or None
+        self.moves = None                   # capture_moves(): the move words of the field as it was then, n_pairs * P int32
+        self._compensated = False           # compensate_camera() has run since the last run_flow()
 
     def synth(self, t0=0, seed=0):
         """fill the resident clip with synthetic frames t0 .. t0+n_frames-1"""
@@ -77,6 +79,10 @@ class ClipPipeline:
             p0 += n
         self._sums_valid = stats
         self._label_k = None                # the labels belong to the field that was just overwritten
+        self._compensated = False
+        if self.moves is not None:          # ... and so do the captured moves
+            self.moves.free()
+            self.moves = None
         if sync:
             self.sync()
 
@@ -251,11 +257,22 @@ class ClipPipeline:
                                         _lib.ptr(status), None, _lib.ptr(moments)))
         self._sums_valid = False
         self._label_k = None
+        self._compensated = True
         check(load().ofc_motion_subtract_dev(self.device, fp, self.W, self.H, n, _lib.ptr(params), fp))
         return cam.motion_from_history(params, status, moments, model)
 
+    def capture_moves(self):
+        """store where the resident field says every pixel goes (blobs.moves_dev: its vectors rounded to whole pixels, one
+        int32 each, on the device) for blobs(links=).  Call it before compensate_camera(): the residual does not say where
+        a pixel lands.  run_flow() discards what was captured."""
+        from . import blobs as bl
+        self.sync()
+        if self.moves is None:
+            self.moves = DeviceBuffer(self.n_pairs * self.W * self.H * 4, self.device)
+        bl.moves_dev(self.flows.ptr, self.W, self.H, self.n_pairs, self.moves.ptr, self.device)
+
     def blobs(self, by="moving", thr=0.5, select=None, merge=False, connectivity=8, min_area=1, max_blobs=4096, labels=True,
-              mean="field"):
+              mean="field", links=None):
         """the moving objects of every resident pair (blobs.py: connected components of a key map, one record each) ->
         blobs.Blobs.  by='moving': the pixels whose vector's length reaches thr, all with key 0 (on hand-held footage call
         compensate_camera first).  by='labels': the label buffer of the last run_kmeans() / assign() is the key map as it
@@ -263,15 +280,27 @@ class ClipPipeline:
         the label assign(centers) would give it, centred by this field's own mean (mean='field'; mean=None labels un-centred,
         as a FlowStream's model does, or pass the two values); select (labels to keep, None = all),
         merge (join neighbouring regions of different labels) and thr (None: no motion test) as blobs.cluster_blobs.
-        The records' mean flow comes from the resident field.  Rank-local: a pair depends on itself alone."""
+        The records' mean flow comes from the resident field.  Rank-local: a pair depends on itself alone.
+        links = a max_links: the blobs of consecutive pairs are linked as well (Blobs.links, Blobs.nlinks; blobs.tracks turns
+        them into track ids), by the moves capture_moves() stored, or, where none were captured, by moves taken from the
+        resident field as it stands; ValueError if compensate_camera() has run since the last run_flow() and no moves were
+        captured, because the residual does not say where a pixel goes.  Links are rank-local too: a transition whose two
+        pairs live on different ranks is not linked."""
         from . import blobs as bl
         self.sync()
         n, W, H = self.n_pairs, self.W, self.H
+        link = {}
+        if links is not None:
+            if self.moves is None and self._compensated:
+                raise ValueError("blobs(links=) after compensate_camera() needs the moves of the whole flow: call "
+                                 "capture_moves() before compensate_camera()")
+            link = dict(links=int(links), moves_ptr=self.moves.ptr if self.moves is not None else None)
         if isinstance(by, str) and by == "labels":
             if self._label_k is None:
                 raise ValueError("blobs(by='labels') needs labels for the resident field: call run_kmeans() or assign() first "
                                  "(run_flow() discards them)")
-            return bl.components_dev(self.labels.ptr, self.flows.ptr, W, H, n, connectivity, min_area, max_blobs, labels, self.device)
+            return bl.components_dev(self.labels.ptr, self.flows.ptr, W, H, n, connectivity, min_area, max_blobs, labels, self.device,
+                                     **link)
         bl.check_args(W, H, n, connectivity, min_area, max_blobs)
         keys = DeviceBuffer(n * W * H, self.device)
         try:
@@ -284,7 +313,8 @@ class ClipPipeline:
                     _, mean, _ = self._centred_model(by)
                 bl.keys_dev(self.flows.ptr, W, H, n, keys.ptr, thr=thr, centers=by, mean=mean, select=select, merge=merge,
                             device=self.device)
-            out = bl.components_dev(keys.ptr, self.flows.ptr, W, H, n, connectivity, min_area, max_blobs, labels, self.device)
+            out = bl.components_dev(keys.ptr, self.flows.ptr, W, H, n, connectivity, min_area, max_blobs, labels, self.device,
+                                    **link)
             out.keys = keys.download((n, H, W), np.uint8)
             return out
         finally:
@@ -306,6 +336,6 @@ class ClipPipeline:
     def close(self):
         for e in self.engines:
             e.close()
-        for b in (self.frames, self.flows, self.labels, self.uv_sums, self.weights):
+        for b in (self.frames, self.flows, self.labels, self.uv_sums, self.weights, self.moves):
             if b is not None:
                 b.free()

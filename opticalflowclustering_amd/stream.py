@@ -7,7 +7,8 @@ pair's field is labelled against the centres and counted per grid cell on the de
 (histogram=(bins, range)) every pair's field is also added to the stream's (u,v) table (uvhist.py), so a model can be fitted
 on such footage too: histogram().fit(k).  With a camera (camera="affine") every pair's camera motion is fitted and subtracted
 on the device straight after the flow (camera.py), and all of the above see the residual field.  With blobs
-(blobs=dict(thr=...)) every pair's moving regions are labelled and described on the device as well (blobs.py): blobs()."""
+(blobs=dict(thr=...)) every pair's moving regions are labelled and described on the device as well (blobs.py): blobs();
+with max_links among them the blobs of consecutive pairs are linked too, inside a batch and across batches (blobs.tracks)."""
 import ctypes as C
 
 import numpy as np
@@ -35,34 +36,49 @@ class FlowStream:
         if camera is not None:
             self.set_camera(camera)
         self.blob_args = None               # (connectivity, thr, min_area, max_blobs) of the stream's blobs, or None
+        self.max_links = 0                  # of the stream's blob links, 0 without them
         if blobs is not None:
             self.set_blobs(**blobs)
 
-    def set_blobs(self, thr=0.5, connectivity=8, min_area=1, max_blobs=4096):
+    def set_blobs(self, thr=0.5, connectivity=8, min_area=1, max_blobs=4096, max_links=0):
         """from the next batch on, find every pair's moving objects (ofc_stream_set_blobs; blobs.py has the definition):
         foreground where the vector's length reaches thr (of the residual field, with a camera), keyed by the model's
         label where the stream has a model, so neighbouring regions of different motion stay apart; without one all keys
-        are 0.  connectivity=None or 0 removes them.  Only on a stream that holds no frame and no undelivered result, as
-        set_model; ValueError otherwise, and nothing changes."""
+        are 0.  connectivity=None or 0 removes them.  max_links > 0 also links the blobs of consecutive pairs
+        (ofc_stream_set_blob_links; blobs.link has the definition): across the pairs of a batch, across batches, by the
+        moves of the field before the camera is removed; a finish ends the chain.  max_links=0 removes the links.  Only on
+        a stream that holds no frame and no undelivered result, as set_model; ValueError otherwise, and nothing changes."""
         if not connectivity:
-            check(load().ofc_stream_set_blobs(self._h, 0, 0.0, 1, 1))
-            self.blob_args = None
+            check(load().ofc_stream_set_blobs(self._h, 0, 0.0, 1, 1))        # removes the links with them
+            self.blob_args, self.max_links = None, 0
             return
+        from .blobs import check_args, check_link_args
         args = (int(connectivity), float(thr), int(min_area), int(max_blobs))
+        check_args(self.W, self.H, 1, args[0], args[2], args[3])             # both calls or neither: refuse before the first
+        if max_links:
+            check_link_args(self.W, self.H, 1, args[2], max_links)
         check(load().ofc_stream_set_blobs(self._h, *args))
         self.blob_args = args
         self._last_pairs = 0
+        check(load().ofc_stream_set_blob_links(self._h, int(max_links)))
+        self.max_links = int(max_links)
 
     def blobs(self):
         """-> blobs.Blobs (records and found; no label map) of the pairs the last finish() / finish_clusters() delivered
         (ofc_stream_read_blobs).  Straight after a finish only; ValueError once frames are held again, and on a stream
-        without blobs."""
-        from .blobs import NF, Blobs, order_records
+        without blobs.  With max_links it carries links and nlinks (ofc_stream_read_blob_links) for blobs.tracks."""
+        from .blobs import LINK_NF, NF, Blobs, _split_links, order_records
         n, mb = self._last_pairs, self.blob_args[3] if self.blob_args else 1
         table = np.zeros((max(n, 1), mb, NF), np.int64)
         cnt, found = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
         check(load().ofc_stream_read_blobs(self._h, ptr(table), ptr(cnt), ptr(found), max(n, 1)))
-        return Blobs(self.W, self.H, None, [order_records(table[i, :cnt[i]], int(cnt[i]), mb) for i in range(n)], found[:n])
+        out = Blobs(self.W, self.H, None, [order_records(table[i, :cnt[i]], int(cnt[i]), mb) for i in range(n)], found[:n])
+        if self.max_links:
+            nt = max(n - 1, 0)
+            links, nlinks = np.zeros((max(nt, 1), self.max_links, LINK_NF), np.int64), np.zeros(max(nt, 1), np.int32)
+            check(load().ofc_stream_read_blob_links(self._h, ptr(links), ptr(nlinks), max(nt, 1)))
+            out.links, out.nlinks = _split_links(links[:nt], nlinks[:nt]), nlinks[:nt]
+        return out
 
     def set_camera(self, camera, thresholds=None):
         """from the next batch on, fit every pair's camera motion and subtract it in place before anything else looks at
