@@ -744,6 +744,66 @@ int ofc_stream_read_blob_links(ofc_stream_t *s, int64_t *links_host, int32_t *nl
 int ofc_bench_blob_links(int device, const int32_t *labels_dev, const float *flow_dev, int W, int H, int npair, int what,
                          int iters, float *ms_per_run);
 
+/* ---- Forward-backward consistency: which vectors of a field survive the check against the field of the reversed pair.
+ * The reference has no counterpart: it trusted every vector of cv2.calcOpticalFlowFarneback alike
+ * (computeOpticalFlowModule.py:20-22).
+ * Definition (normative, like the text above; every output is an integer).
+ * Inputs: fwd f32 [npair][H][W][2], pair t being frame t -> t+1 on frame t's grid; bwd of the same shape, the field frame
+ * t+1 -> t on frame t+1's grid.  With bwd_reversed = 0 pair t's backward field is bwd[t], with bwd_reversed = 1 it is
+ * bwd[npair-1-t]: what the flow engine leaves when it is run over the clip with its frames in reverse order.
+ * Q(u) = llrint((double)u * 65536).  A vector is valid exactly as the camera and blob blocks have it: u, v finite and
+ * |u|, |v| < 1024.  For pixel (x, y) of pair t with a valid forward vector, X = x*65536 + Q(u), Y = y*65536 + Q(v).
+ * Landing: the pixel lands inside iff 0 <= X <= (W-1) << 16 and 0 <= Y <= (H-1) << 16.  ix = X >> 16, fx = X & 65535, iy and
+ * fy likewise.  The four taps are (ix, iy), (min(ix+1, W-1), iy), (ix, min(iy+1, H-1)), (min(ix+1, W-1), min(iy+1, H-1)) with
+ * the weights (65536-fx)(65536-fy), fx(65536-fy), (65536-fx)fy, fx*fy (they sum to 2^32); all four taps must be valid
+ * vectors of the backward field.
+ * Interpolated backward vector, per component: S = sum of w_i * Q(b_i) in int64 (|S| <= 2^58), B = (S + 2^31) >> 32 with an
+ * arithmetic shift.  Residual e = (Q(u) + Bx, Q(v) + By); d2 = ex^2 + ey^2; m2 = Q(u)^2 + Q(v)^2 + Bx^2 + By^2.
+ * Verdict: consistent iff d2 <= (m2 >> 16) * alpha_q + beta_q, which is |f + b|^2 <= alpha (|f|^2 + |b|^2) + beta with
+ * alpha = alpha_q / 65536 and beta = beta_q / 2^32 px^2.  alpha_q in 0 .. 65536, beta_q in 0 .. 2^62; nothing overflows
+ * int64 (d2 < 2^55, the right side < 2^54 + 2^62).
+ * Outputs: state u8 [npair][H][W], one of the four OFC_CONSIST_* below, decided in this order: the forward vector is
+ * invalid -> INVALID; it lands outside -> LEAVES; a tap is invalid -> INVALID; else the comparison.  counts int64
+ * [npair][4]: the pixels of the pair in each state.  Optionally resid int32 [npair][H][W][2]: e for the states CONSISTENT
+ * and MISMATCH, zero otherwise.
+ * Limits: W, H in 1 .. 16384, so that X and Y fit int32 (above: OFC_EUNSUPPORTED); npair in 1 .. 65535, alpha_q and beta_q
+ * in their ranges, bwd_reversed 0 or 1 (otherwise, and for W, H < 1: OFC_EINVAL). ---- */
+#define OFC_CONSIST_OK 0        /* consistent */
+#define OFC_CONSIST_MISMATCH 1  /* the two fields do not cancel */
+#define OFC_CONSIST_LEAVES 2    /* the pixel leaves the frame */
+#define OFC_CONSIST_INVALID 3   /* the forward vector is invalid, or the pixel lands inside and a tap is invalid */
+#define OFC_CONSIST_STATES 4
+#define OFC_CONSIST_SHARE 2048  /* consecutive pixels of a pair a work-group of the check kernel takes */
+#define OFC_CONSIST_MAX_DIM 16384
+#define OFC_CONSIST_ALPHA_MAX 65536
+#define OFC_CONSIST_BETA_MAX ((int64_t)1 << 62)
+/* Host only, no device is touched: OFC_OK iff the arguments are inside the limits above.  Every call below decides by it
+ * before anything is allocated or launched.  No counterpart in the reference, as for every call of this block. */
+int ofc_consist_check(int W, int H, int npair, int64_t alpha_q, int64_t beta_q);
+/* fwd_dev, bwd_dev f32 [npair][H][W][2] (8-byte aligned; the forward field is read with 16-byte loads where every pair's
+ * base allows) -> state_dev u8 [npair][H][W], counts_dev int64 [npair][4] (8-byte aligned; cleared here), and resid_dev int32
+ * [npair][H][W][2] (8-byte aligned) unless it is NULL.  Every tap index is clamped into the frame before it indexes
+ * anything, whatever the fields hold.  Neither field is written.  Returns when done. */
+int ofc_consist_dev(int device, const float *fwd_dev, const float *bwd_dev, int W, int H, int npair, int bwd_reversed,
+                    int64_t alpha_q, int64_t beta_q, uint8_t *state_dev, int64_t *counts_dev, int32_t *resid_dev);
+/* The whole chain on host buffers of the same shapes; resid_host may be NULL. */
+int ofc_consist(int device, const float *fwd_host, const float *bwd_host, int W, int H, int npair, int bwd_reversed,
+                int64_t alpha_q, int64_t beta_q, uint8_t *state_host, int64_t *counts_host, int32_t *resid_host);
+/* state_dev u8 [n] and a set `keep` of states (bit s = state s, 0 .. 15): where bit state[p] of keep is clear (a byte above 3
+ * is in no set), keys_dev[p] = 255 (the background of a blob key map) and w_dev[p] = 0.0f (a sample weight); everything else
+ * is left as it is.  keys_dev u8 [n] and w_dev f32 [n] (4-byte aligned) may each be NULL; 16 elements per lane where all
+ * bases given are 16-byte aligned, with a scalar tail.  n >= 1.  Returns when done. */
+int ofc_consist_mask_dev(int device, const uint8_t *state_dev, int64_t n, int keep, uint8_t *keys_dev, float *w_dev);
+/* frames_dev u8 [n_frames][H][W] -> out_dev of the same shape with the frames in reverse order (out[i] = frames[n-1-i]);
+ * the two must not overlap.  W, H >= 1, n_frames in 1 .. 65536.  Returns when done. */
+int ofc_frames_reverse_dev(int device, const uint8_t *frames_dev, int W, int H, int n_frames, uint8_t *out_dev);
+/* Measurement hook: average duration by HIP events over `iters` runs, two warm-up runs before them, on fwd_dev and bwd_dev
+ * (bwd_reversed 0, alpha_q 655, beta_q 2^31) with outputs of the hook's own.  what = 0: the check without the residual (the
+ * clear of the counts included); 1: the check with it; 2: the mask on a key map and a weight array, keep = {0}, after one
+ * untimed check. */
+int ofc_bench_consist(int device, const float *fwd_dev, const float *bwd_dev, int W, int H, int npair, int what, int iters,
+                      float *ms_per_run);
+
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.

@@ -18,6 +18,9 @@ UV_HIST_SHARE = 2048      # OFC_UV_HIST_SHARE: consecutive vectors a work-group 
 UV_HIST_MAX_GRID = 2048   # OFC_UV_HIST_MAX_GRID: most work-groups of one histogram launch
 BLOB_TILE_W, BLOB_TILE_H, BLOB_FIELDS = 64, 16, 12   # OFC_BLOB_TILE_W, OFC_BLOB_TILE_H, OFC_BLOB_FIELDS
 BLOB_LINK_FIELDS, BLOB_NO_MOVE = 3, -0x7fff8000      # OFC_BLOB_LINK_FIELDS; OFC_BLOB_NO_MOVE (0x80008000) as an int32
+CONSIST_OK, CONSIST_MISMATCH, CONSIST_LEAVES, CONSIST_INVALID, CONSIST_STATES = 0, 1, 2, 3, 4   # OFC_CONSIST_*
+CONSIST_SHARE, CONSIST_MAX_DIM = 2048, 16384         # OFC_CONSIST_SHARE, OFC_CONSIST_MAX_DIM
+CONSIST_ALPHA_MAX, CONSIST_BETA_MAX = 65536, 1 << 62  # OFC_CONSIST_ALPHA_MAX, OFC_CONSIST_BETA_MAX
 
 
 class OfcError(RuntimeError):
@@ -154,6 +157,12 @@ _PROTOS = {
     "ofc_stream_set_blob_links": ([_vp, _i], _i),
     "ofc_stream_read_blob_links": ([_vp, _vp, _vp, _i], _i),
     "ofc_bench_blob_links": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
+    "ofc_consist_check": ([_i, _i, _i, _i64, _i64], _i),
+    "ofc_consist_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp], _i),
+    "ofc_consist": ([_i, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp], _i),
+    "ofc_consist_mask_dev": ([_i, _vp, _i64, _i, _vp, _vp], _i),
+    "ofc_frames_reverse_dev": ([_i, _vp, _i, _i, _i, _vp], _i),
+    "ofc_bench_consist": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

@@ -34,6 +34,12 @@ out of the resident route, --stream and --fit-stream, with --camera after the ca
 With --tracks (it needs --blobs) the blobs of consecutive pairs are linked on the device as well (blobs.link: a blob's pixels
 land, by their own flow vectors before the camera is removed, on the next pair's blobs) and every row gets a last column,
 the id of the track its blob belongs to (blobs.tracks).
+
+With --consistent (resident route only) the flow is computed a second time over the reversed clip and every vector is put
+to the forward-backward check on the device (consistency.py), before any camera removal: the fit then gives weight 0 to
+every pixel that failed it, and the --blobs key map keeps only those that passed.  --fb-alpha and --fb-beta are the check's
+two constants (the literature's 0.01 and 0.5 px^2 by default, not tuned here); --fb-counts writes the (pairs, 4) pixel
+counts per state.
 """
 import argparse
 import os
@@ -161,7 +167,23 @@ def parse_arguments(argv=None):
     ap.add_argument("--blob-connectivity", type=int, choices=(4, 8), default=8)
     ap.add_argument("--tracks", action="store_true",
                     help="link the blobs of consecutive pairs and add a track id as the last column of the --blobs file")
+    ap.add_argument("--consistent", action="store_true",
+                    help="forward-backward check of every vector (resident route): failed pixels get weight 0 and no blob")
+    ap.add_argument("--fb-alpha", type=float, default=0.01, help="relative term of the check (a convention, not tuned)")
+    ap.add_argument("--fb-beta", type=float, default=0.5, help="absolute term of the check in px^2 (a convention, not tuned)")
+    ap.add_argument("--fb-counts", metavar="FILE.npy", help="write the (pairs, 4) pixel counts per state to this .npy file")
     args = ap.parse_args(argv)
+    if args.consistent:
+        for flag, given in (("--stream", args.stream), ("--fit-stream", args.fit_stream)):
+            if given:
+                ap.error(f"--consistent needs the resident clip (a stream would need the engine a second time): not with {flag}")
+        from .consistency import quantise
+        try:
+            quantise(args.fb_alpha, args.fb_beta)
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.fb_counts or args.fb_alpha != 0.01 or args.fb_beta != 0.5:
+        ap.error("--fb-alpha, --fb-beta and --fb-counts belong to --consistent")
     if args.camera_out and args.camera == "none":
         ap.error("--camera-out needs --camera translation or --camera affine")
     args.camera_spec = None if args.camera == "none" else (args.camera, args.camera_thresholds)
@@ -299,6 +321,16 @@ def main(argv=None):
     try:
         pipe.upload_frames(frames)
         pipe.run_flow()
+        fb = args.consistent
+        if fb:                                  # before the camera is taken out: a residual does not say where a pixel lands
+            from .consistency import STATE_NAMES
+            pipe.run_backward_flow()
+            checked = pipe.consistency(args.fb_alpha, args.fb_beta)
+            print("forward-backward check: " + ", ".join(f"{100.0 * s:.2f} % {name}" for name, s in
+                                                         zip(STATE_NAMES, checked.counts.sum(0) / max(checked.counts.sum(), 1))))
+            if args.fb_counts:
+                os.makedirs(os.path.dirname(args.fb_counts) or ".", exist_ok=True)
+                np.save(args.fb_counts, checked.counts)
         if args.camera_spec:
             if args.max_links:
                 pipe.capture_moves()            # where the pixels go: before the camera is taken out of the field
@@ -309,15 +341,16 @@ def main(argv=None):
             centers = given
             pipe.assign(centers)
         elif given is not None:
-            centers, _, _ = pipe.run_kmeans(given, sample_weight=args.weights)
-        elif args.weights is not None:          # sklearn's weighted k-means++ fit in its two-step form
-            C0, _ = pipe.seed_kmeans(k, args.seed, sample_weight=args.weights)
-            centers, _, _ = pipe.run_kmeans(C0, sample_weight=args.weights)
+            centers, _, _ = pipe.run_kmeans(given, sample_weight=args.weights, consistent=fb)
+        elif args.weights is not None or fb:    # sklearn's weighted k-means++ fit in its two-step form
+            C0, _ = pipe.seed_kmeans(k, args.seed, sample_weight=args.weights, consistent=fb)
+            centers, _, _ = pipe.run_kmeans(C0, sample_weight=args.weights, consistent=fb)
         else:
             centers, _, _ = pipe.run_kmeans("k-means++", k=k, random_state=args.seed)
         counts = pipe.cell_clusters(args.rows, args.cols)
         if args.blob_spec:
-            write_blob_csv(args.blobs, pipe.blobs(by=centers, mean=None, labels=False, links=args.max_links or None, **args.blob_spec),
+            write_blob_csv(args.blobs, pipe.blobs(by=centers, mean=None, labels=False, links=args.max_links or None,
+                                                  consistent=fb, **args.blob_spec),
                            tracks=bool(args.max_links))
     finally:
         pipe.close()

@@ -58,6 +58,9 @@ class ClipPipeline:
         self._label_k = None                # the k the resident labels were written with (run_kmeans / assign), or None
         self.moves = None                   # capture_moves(): the move words of the field as it was then, n_pairs * P int32
         self._compensated = False           # compensate_camera() has run since the last run_flow()
+        self.frames_rev = None              # run_backward_flow(): the resident frames in reverse order, n_frames * P u8
+        self.flows_bwd = None               # ... and the field of that clip: pair t's backward field at n_pairs-1-t
+        self.state = None                   # consistency(): the state map of the forward-backward check, n_pairs * P u8
 
     def synth(self, t0=0, seed=0):
         """fill the resident clip with synthetic frames t0 .. t0+n_frames-1"""
@@ -83,14 +86,87 @@ class ClipPipeline:
         if self.moves is not None:          # ... and so do the captured moves
             self.moves.free()
             self.moves = None
+        self._drop_backward()               # ... and the backward field and the state map checked against it
         if sync:
             self.sync()
+
+    def _drop_backward(self):
+        for name in ("frames_rev", "flows_bwd", "state"):
+            b = getattr(self, name)
+            if b is not None:
+                b.free()
+                setattr(self, name, None)
+
+    def run_backward_flow(self, sync=True):
+        """the backward field of every resident pair, for consistency(): the resident frames are copied in reverse order into
+        a buffer of the pipeline's own (consistency.frames_reverse_dev) and the flow runs over that clip with run_flow()'s
+        schedule on the same engines, into flows_bwd.  Pair t of that field is frame n-1-t -> n-2-t, so the backward field
+        of forward pair t sits at n_pairs-1-t (the library's bwd_reversed = 1).  Costs what run_flow() costs, and as much
+        memory again for the field.  run_flow() discards it."""
+        from . import consistency as cons
+        P = self.W * self.H
+        self.sync()
+        self._drop_backward()
+        self.frames_rev = DeviceBuffer(self.n_frames * P, self.device)
+        self.flows_bwd = DeviceBuffer(self.n_pairs * P * 8, self.device)
+        cons.frames_reverse_dev(self.frames.ptr, self.W, self.H, self.n_frames, self.frames_rev.ptr, self.device)
+        p0 = 0
+        for i, n in enumerate(self.schedule):
+            self.engines[i % len(self.engines)].calc_frames_dev(self.frames_rev.ptr + p0 * P, n + 1,
+                                                                self.flows_bwd.ptr + p0 * P * 8, sync=False)
+            p0 += n
+        if sync:
+            self.sync()
+
+    def flows_bwd_host(self):
+        """host copy of run_backward_flow()'s field, in the order it has on the device (the reversed clip's)"""
+        if self.flows_bwd is None:
+            raise ValueError("no backward field: call run_backward_flow() first (run_flow() discards it)")
+        self.sync()
+        return self.flows_bwd.download((self.n_pairs, self.H, self.W, 2), np.float32)
+
+    def consistency(self, alpha=0.01, beta=0.5, residual=False):
+        """the forward-backward check of the resident field against run_backward_flow()'s (consistency.py; ofc_consist_dev)
+        -> consistency.Consistency.  The state map also stays on the device, for blobs(consistent=True) and
+        run_kmeans / seed_kmeans(consistent=True), until the next run_flow().  alpha, beta: consistency.check's, a
+        convention of the literature and not tuned here.  ValueError without a backward field, and after
+        compensate_camera(): a residual does not say where a pixel lands (the rule blobs(links=) has), so check before the
+        camera is removed.  Rank-local: a pair depends on itself alone."""
+        from . import consistency as cons
+        alpha_q, beta_q = cons.quantise(alpha, beta)
+        if self.flows_bwd is None:
+            raise ValueError("consistency() needs the backward field: call run_backward_flow() first (run_flow() discards it)")
+        if self._compensated:
+            raise ValueError("consistency() after compensate_camera() would follow the residual, which does not say where a "
+                             "pixel lands: call it before compensate_camera()")
+        self.sync()
+        n, W, H = self.n_pairs, self.W, self.H
+        if self.state is None:
+            self.state = DeviceBuffer(n * W * H, self.device)
+        try:
+            counts, resid = cons.check_dev(self.flows.ptr, self.flows_bwd.ptr, W, H, n, self.state.ptr, alpha_q, beta_q,
+                                           bwd_reversed=True, residual=residual, device=self.device)
+        except Exception:
+            self.state.free()
+            self.state = None
+            raise
+        return cons.Consistency(self.state.download((n, H, W), np.uint8), counts, resid, alpha_q, beta_q)
+
+    def _state_ptr(self, what):
+        if self.state is None:
+            raise ValueError(f"{what} needs the state map of the forward-backward check: call run_backward_flow() and "
+                             "consistency() first (run_flow() discards them)")
+        return self.state.ptr
 
     def sync(self):
         for e in self.engines:
             e.sync()
 
-    def _weights_ptr(self, sample_weight, N):
+    def _weights_ptr(self, sample_weight, N, consistent=False):
+        if consistent:
+            state_ptr = self._state_ptr("consistent=True")
+            if sample_weight is None:
+                sample_weight = ("moving", 0.0)
         if sample_weight is None:
             return None
         if self.weights is None:
@@ -108,6 +184,9 @@ class ClipPipeline:
             if not np.isfinite(w).all() or (w < 0).any():
                 raise ValueError("sample_weight must be finite and >= 0")
             self.weights.upload(w)
+        if consistent:                      # a pixel that failed the check counts for nothing
+            from . import consistency as cons
+            cons.mask_dev(state_ptr, N, w_ptr=self.weights.ptr, device=self.device)
         return self.weights.ptr
 
     def _colsum(self):
@@ -119,18 +198,20 @@ class ClipPipeline:
             colsum += per_batch[b]
         return colsum
 
-    def seed_kmeans(self, k, random_state=None, n_global=None, sample_weight=None):
+    def seed_kmeans(self, k, random_state=None, n_global=None, sample_weight=None, consistent=False):
         """sklearn's k-means++ seeding on the resident (u,v) vectors (cluster.kmeans_plusplus_dev), with sample_weight as
         in run_kmeans: the weights then decide the first centre, every later draw and every candidate's potential, as in
         sklearn's fit(X, sample_weight=).  run_kmeans(C0, sample_weight=...) from the returned centres completes that fit.
-        None gives the seeds run_kmeans('k-means++', k=k) starts from.  -> (centers (k,2), GLOBAL indices)"""
+        None gives the seeds run_kmeans('k-means++', k=k) starts from.  consistent as in run_kmeans.
+        -> (centers (k,2), GLOBAL indices)"""
         self.sync()
         N = self.n_pairs * self.W * self.H
-        wptr = self._weights_ptr(sample_weight, N)
+        wptr = self._weights_ptr(sample_weight, N, consistent)
         return kmeans_plusplus_dev(self.flows.ptr, _lib.F32, N, 2, int(k), random_state, device=self.device,
                                    colsum=self._colsum(), n_global=n_global, weights_ptr=wptr, weight_dtype=_lib.F32)
 
-    def run_kmeans(self, init, max_iter=300, tol=1e-4, k=None, random_state=None, n_global=None, sample_weight=None):
+    def run_kmeans(self, init, max_iter=300, tol=1e-4, k=None, random_state=None, n_global=None, sample_weight=None,
+                   consistent=False):
         """Lloyd over all local (u,v) vectors (global when a communicator is active).
         init: (k,2) array, or 'k-means++' with k= and random_state=: sklearn's seeding on the resident vectors
         (cluster.kmeans_plusplus_dev).  Under a communicator every rank passes the same random_state, and n_global = the
@@ -138,13 +219,16 @@ class ClipPipeline:
         sample_weight: None, 'magnitude' (a vector counts by its length), ('moving', thr) (1 where the length reaches thr,
         else 0), or one value per local vector (kept as f32).  The weights live in a device buffer allocated on first use;
         not available together with init='k-means++' in one call (seed_kmeans(k, sample_weight=...) first, then pass its
-        centres as init).  -> centers (k,2), inertia, n_iter"""
+        centres as init).
+        consistent=True: the weight of every pixel whose state in consistency()'s map is not CONSISTENT becomes 0
+        (ofc_consist_mask_dev on the weight buffer); with sample_weight=None the weights start from ('moving', 0.0).  It
+        makes the fit a weighted one, so the rule about init='k-means++' applies.  -> centers (k,2), inertia, n_iter"""
         self.sync()
         N = self.n_pairs * self.W * self.H
-        if sample_weight is not None and isinstance(init, str):
-            raise ValueError("sample_weight together with init='k-means++' is not supported in one call: seed first, "
-                             "C0, _ = seed_kmeans(k, random_state, sample_weight=...), then run_kmeans(C0, sample_weight=...)")
-        wptr = self._weights_ptr(sample_weight, N)
+        if (sample_weight is not None or consistent) and isinstance(init, str):
+            raise ValueError("sample_weight or consistent=True together with init='k-means++' is not supported in one call: seed "
+                             "first, C0, _ = seed_kmeans(k, random_state, sample_weight=...), then run_kmeans(C0, sample_weight=...)")
+        wptr = self._weights_ptr(sample_weight, N, consistent)
         colsum = self._colsum()
         if isinstance(init, str):
             if init != "k-means++" or k is None:
@@ -272,7 +356,7 @@ class ClipPipeline:
         bl.moves_dev(self.flows.ptr, self.W, self.H, self.n_pairs, self.moves.ptr, self.device)
 
     def blobs(self, by="moving", thr=0.5, select=None, merge=False, connectivity=8, min_area=1, max_blobs=4096, labels=True,
-              mean="field", links=None):
+              mean="field", links=None, consistent=False):
         """the moving objects of every resident pair (blobs.py: connected components of a key map, one record each) ->
         blobs.Blobs.  by='moving': the pixels whose vector's length reaches thr, all with key 0 (on hand-held footage call
         compensate_camera first).  by='labels': the label buffer of the last run_kmeans() / assign() is the key map as it
@@ -285,10 +369,18 @@ class ClipPipeline:
         them into track ids), by the moves capture_moves() stored, or, where none were captured, by moves taken from the
         resident field as it stands; ValueError if compensate_camera() has run since the last run_flow() and no moves were
         captured, because the residual does not say where a pixel goes.  Links are rank-local too: a transition whose two
-        pairs live on different ranks is not linked."""
+        pairs live on different ranks is not linked.
+        consistent=True: the key map is masked to the pixels that consistency() found CONSISTENT before the components are
+        found (ofc_consist_mask_dev: every other pixel becomes background).  ValueError with by='labels', whose key map is
+        the label buffer itself, and without a state map."""
         from . import blobs as bl
         self.sync()
         n, W, H = self.n_pairs, self.W, self.H
+        if consistent:
+            if isinstance(by, str) and by == "labels":
+                raise ValueError("blobs(by='labels', consistent=True): that key map is the label buffer itself and is not "
+                                 "masked; key by 'moving' or by centres")
+            state_ptr = self._state_ptr("blobs(consistent=True)")
         link = {}
         if links is not None:
             if self.moves is None and self._compensated:
@@ -313,6 +405,9 @@ class ClipPipeline:
                     _, mean, _ = self._centred_model(by)
                 bl.keys_dev(self.flows.ptr, W, H, n, keys.ptr, thr=thr, centers=by, mean=mean, select=select, merge=merge,
                             device=self.device)
+            if consistent:
+                from . import consistency as cons
+                cons.mask_dev(state_ptr, n * W * H, keys_ptr=keys.ptr, device=self.device)
             out = bl.components_dev(keys.ptr, self.flows.ptr, W, H, n, connectivity, min_area, max_blobs, labels, self.device,
                                     **link)
             out.keys = keys.download((n, H, W), np.uint8)
@@ -336,6 +431,7 @@ class ClipPipeline:
     def close(self):
         for e in self.engines:
             e.close()
+        self._drop_backward()
         for b in (self.frames, self.flows, self.labels, self.uv_sums, self.weights, self.moves):
             if b is not None:
                 b.free()
