@@ -219,12 +219,33 @@ int ofc_kmeans_fit_dev(int device, const void *X_dev, int dtype, int64_t N, int 
 int ofc_kmeans_fit_dev_stats(int device, const void *X_dev, int dtype, int64_t N, int d, int k,
                              const double *init, int max_iter, double tol_rel, const double *colsum,
                              double *centers, uint8_t *labels_dev, double *inertia, int *n_iter);
+/* ofc_kmeans_fit_dev_stats for a caller that knows what X_dev is: a stack of n_fields flow fields, X_dev[n_fields][H][W][2]
+ * float32 (dtype OFC_F32, d = 2, N = n_fields * W * H; anything else: OFC_EINVAL), e.g. the field of
+ * computeOpticalFlow.py:99-101 for every frame pair of a clip, or this rank's whole pairs under a communicator.  The result
+ * is ofc_kmeans_fit_dev_stats': the geometry only changes how the tile sweeps of ofc_lloyd_prune_stats cut the samples.
+ * When W % 64 == 0 and H % 8 == 0 (and k <= 8, OFC_LLOYD_PRUNE != 0) a tile is 16 x 4 pixels instead of a 64 x 1 row
+ * segment, and 8 tiles form a 64 x 8-pixel group that is tested first: a motion boundary is a curve in the image, and
+ * compact tiles lose a quarter of the samples to it that row segments lose.  Other sizes run the 64 x 1 tiles. */
+int ofc_kmeans_fit_dev_field(int device, const void *X_dev, int dtype, int64_t N, int d, int k,
+                             const double *init, int max_iter, double tol_rel, const double *colsum,
+                             double *centers, uint8_t *labels_dev, double *inertia, int *n_iter,
+                             int W, int H, int64_t n_fields);
+/* The tile -> sample map of ofc_kmeans_fit_dev_field (host arithmetic, no device needed): the index, into the stack's
+ * n_fields * H * W samples, of the first of the 4 consecutive samples that quad `quad` (0..15) of tile `tile` covers, for
+ * fields of width W (a multiple of 64; the map does not depend on H, which is a multiple of 8).  Tiles are numbered
+ * group-major: tile = 8 * group + (tile row of the group) * (tiles across a group) + (tile column).  -1: bad arguments.
+ * ofc_lloyd_field_origins: the same for the 16 quads of each of n_tiles tiles from tile0 on, out[n_tiles][16].
+ * ofc_lloyd_field_shape: the tile's and the group's size in pixels. */
+int64_t ofc_lloyd_field_origin(int64_t tile, int quad, int W);
+int ofc_lloyd_field_origins(int64_t tile0, int64_t n_tiles, int W, int64_t *out);
+void ofc_lloyd_field_shape(int *tile_w, int *tile_h, int *group_w, int *group_h);
 /* How the last ofc_kmeans_fit_dev[_stats] on `device` swept its samples (no reference counterpart: sklearn's Lloyd,
  * _k_means_lloyd.pyx:23-218, reads every sample in every iteration).  For a float32 d=2 stream (the per-pixel (u,v) vectors
  * of computeOpticalFlow.py:99-101's field) of >= 2^20 samples and k <= 8 the label-less iterations run over 64-sample
  * tiles; a tile whose (u,v) bounding box lies inside one Voronoi cell of the current centres contributes its cached sum
  * without being read, in the iterations and in the final E-step (exact: same labels, same n_iter, centres and inertia equal
- * to rounding).  out6 = [tile sweeps, of them pruned,
+ * to rounding).  After ofc_kmeans_fit_dev_field on a field it can cut in 2-D the tiles are 16 x 4 pixels under 64 x 8-pixel
+ * groups; the counts stay in tiles (a group that passes counts as 8 tiles tested and 8 skipped).  out6 = [tile sweeps, of them pruned,
  * tiles tested by the pruned sweeps, tiles they skipped, probe sweeps, 1 if the final E-step ran pruned].  Environment: OFC_LLOYD_PRUNE=0 switches
  * the tile sweeps off, 2 enables them for any N, 3 also forces every one of them to run pruned. */
 int ofc_lloyd_prune_stats(int device, double *out6);

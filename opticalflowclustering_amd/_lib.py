@@ -85,6 +85,10 @@ _PROTOS = {
     "ofc_kmeans_predict": ([_i, _vp, _i, _i64, _i, _i, _vp, _vp], _i),
     "ofc_kmeans_fit_dev": ([_i, _vp, _i, _i64, _i, _i, _vp, _i, _d, _vp, _vp, C.POINTER(_d), _ip], _i),
     "ofc_kmeans_fit_dev_stats": ([_i, _vp, _i, _i64, _i, _i, _vp, _i, _d, _vp, _vp, _vp, C.POINTER(_d), _ip], _i),
+    "ofc_kmeans_fit_dev_field": ([_i, _vp, _i, _i64, _i, _i, _vp, _i, _d, _vp, _vp, _vp, C.POINTER(_d), _ip, _i, _i, _i64], _i),
+    "ofc_lloyd_field_origin": ([_i64, _i, _i], _i64),
+    "ofc_lloyd_field_origins": ([_i64, _i64, _i, _vp], _i),
+    "ofc_lloyd_field_shape": ([_ip, _ip, _ip, _ip], None),
     "ofc_lloyd_prune_stats": ([_i, _vp], _i),
     "ofc_bench_lloyd_sweep": ([_i, _vp, _i64, _i, _vp, _vp, _i, _i, C.POINTER(_f)], _i),
     "ofc_lloyd_colstats_dev": ([_i, _vp, _i, _i64, _i, _vp, _i, _vp], _i),

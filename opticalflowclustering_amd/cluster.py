@@ -283,11 +283,14 @@ class KMeans:
 
 
 def kmeans_fit_dev(X_ptr, dtype, N, d, init, max_iter=300, tol=1e-4, labels_ptr=None, device=0, colsum=None,
-                   weights_ptr=None, weight_dtype=_lib.F32):
+                   weights_ptr=None, weight_dtype=_lib.F32, field=None):
     """device-resident X (this rank's shard when a communicator is active).  colsum: this rank's column sums when the
     caller already has them (the flow engine emits sum(u), sum(v) with the field): the fit then skips that sweep.
     weights_ptr: N device-resident sample weights of weight_dtype (F32 or F64; finite, >= 0, not all zero over the ranks),
     sklearn's fit(X, sample_weight=); None: the unweighted fit.
+    field=(W, H): X is a stack of N / (W*H) whole float32 (u,v) fields of that size (ofc_kmeans_fit_dev_field): the same
+    result, and the tile sweeps cut the fields in 2-D where W % 64 == 0 and H % 8 == 0.  A weighted fit ignores it (its
+    sweeps read every sample).
     -> centers (k,d), inertia, n_iter"""
     C0 = np.ascontiguousarray(init, np.float64)
     k = C0.shape[0]
@@ -300,6 +303,14 @@ def kmeans_fit_dev(X_ptr, dtype, N, d, init, max_iter=300, tol=1e-4, labels_ptr=
         check(load().ofc_kmeans_fit_dev_w(device, C.c_void_p(X_ptr), dtype, C.c_void_p(weights_ptr), weight_dtype, N, d, k, ptr(C0),
                                           max_iter, tol, ptr(cs), ptr(centers), C.c_void_p(labels_ptr) if labels_ptr else None,
                                           C.byref(inertia), C.byref(n_iter)))
+        return centers, inertia.value, n_iter.value
+    if field is not None:
+        W, H = (int(v) for v in field)
+        if W < 1 or H < 1 or N % (W * H):
+            raise ValueError(f"field={field!r}: N={N} is not a whole number of {W}x{H} fields")
+        check(load().ofc_kmeans_fit_dev_field(device, C.c_void_p(X_ptr), dtype, N, d, k, ptr(C0), max_iter, tol, ptr(cs),
+                                              ptr(centers), C.c_void_p(labels_ptr) if labels_ptr else None, C.byref(inertia),
+                                              C.byref(n_iter), W, H, N // (W * H)))
         return centers, inertia.value, n_iter.value
     check(load().ofc_kmeans_fit_dev_stats(device, C.c_void_p(X_ptr), dtype, N, d, k, ptr(C0), max_iter, tol, ptr(cs), ptr(centers),
                                           C.c_void_p(labels_ptr) if labels_ptr else None, C.byref(inertia), C.byref(n_iter)))

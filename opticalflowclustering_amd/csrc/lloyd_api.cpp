@@ -23,7 +23,7 @@ static size_t dtype_size(int dtype) { return dtype == OFC_U8 ? 1 : (dtype == OFC
 // pinned memory per call dominated small fits (rocprof hip-trace of a 38-frame shard).
 struct LloydScratch {
     DevBuf state, partial, tot, tot_local, excl, far, labels;
-    DevBuf tile_box, tile_sum, tile_sq;  // lloyd_tiles.hip: 16 + 16 + 8 B per 64-sample tile, rebuilt by every fit (k_tile_meta)
+    DevBuf tile_block;                   // lloyd_tiles.hip: the tile (and group) records, rebuilt by every fit (k_tile_meta)
     DevBuf tile_meta;                    // k_tile_meta's reduced record (4 doubles)
     DevBuf kpp_closest, kpp_cs, kpp_ss;  // lloyd_seed.hip: closest[N], chunk sums [8][N / OFC_KPP_CHUNK], their sums per 1024
     DevBuf kpp_io;                       // seeding: [8 indices | 8 x LLOYD_DMAX rows | 192 doubles of all-reduce staging]
@@ -48,6 +48,24 @@ struct LloydScratch {
         OFC_HIP(hipHostMalloc((void **)&status, sizeof(LloydStatus) * LLOYD_WINDOW, hipHostMallocMapped));
         OFC_HIP(hipHostGetDevicePointer((void **)&status_dev, status, 0));
         ready = true;
+        return OFC_OK;
+    }
+    // The records of the tile sweeps over N samples: box 16 + sum 16 + scatter 8 B per 64-sample tile and, for a stack of
+    // fields of width W > 0, the same per 512-sample group.  One block, grown as a whole: a failed allocation leaves it
+    // empty (DevBuf::alloc releases first), so no later fit can meet one array that grew next to one that did not.
+    int tile_bufs(int64_t N, int W, LloydFieldBufs &f)
+    {
+        const size_t nt = (size_t)(N >> 6), ng = W > 0 ? nt >> 3 : 0;
+        const size_t goff = (nt * 40 + 15) & ~(size_t)15, need = goff + ng * 40 + 16;
+        if (tile_block.bytes < need) OFC_TRY(tile_block.alloc(need));
+        char *p = tile_block.as<char>();
+        f.box = p;
+        f.tsum = p + nt * 16;
+        f.tsq = p + nt * 32;
+        f.gbox = p + goff;
+        f.gsum = p + goff + ng * 16;
+        f.gsq = p + goff + ng * 32;
+        f.W = W;
         return OFC_OK;
     }
 };
@@ -175,7 +193,7 @@ static int relocate_empty(LloydScratch &sc, const void *X, int dtype, int64_t N,
 static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d, int k, const double *init,
                          int max_iter, double tol_rel, double *centers, uint8_t *labels_dev,
                          double *inertia, int *n_iter, const double *colsum = nullptr, const void *wdev = nullptr,
-                         int w_dtype = OFC_F32)
+                         int w_dtype = OFC_F32, int field_w = 0, int field_h = 0, int64_t n_fields = 0)
 {
     OFC_REQUIRE(X && init && centers, "null pointer");
     OFC_REQUIRE(dtype >= OFC_U8 && dtype <= OFC_F64, "bad dtype %d", dtype);
@@ -228,14 +246,16 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
     OFC_HIP(hipMemcpyAsync(st->centers, c0, sizeof(double) * k * d, hipMemcpyHostToDevice, s));
     // a weighted fit runs the plain sweeps: the tile metadata (cached per-tile sums) is unweighted
     const int prune = wdev ? LLOYD_PRUNE_OFF : prune_policy_for(dtype, N, d, k);
-    if (prune) {
-        const size_t need = (size_t)(N >> 6) * 16;
-        if (sc.tile_box.bytes < need) {
-            OFC_TRY(sc.tile_box.alloc(need));
-            OFC_TRY(sc.tile_sum.alloc(need));
-            OFC_TRY(sc.tile_sq.alloc(need / 2));
-        }
-    }
+    // X is a stack of fields that the 2-D tiles fit (lloyd_field.h): the tile sweeps take their field form.  Any other
+    // shape runs the 64 x 1 tiles; the result is the same either way.
+    const bool field = prune && field_w > 0 && field_geometry_ok(field_w, field_h, n_fields);
+    LloydFieldBufs tb = {};
+    if (prune) OFC_TRY(sc.tile_bufs(N, field ? field_w : 0, tb));
+    auto tiles_launch = [&](uint8_t *lab, int what, const double *meta) -> int {
+        if (field) return launch_lloyd_tiles_field((const float *)X, N, k, st, tb, lab, sc.partial.as<double>(), nblocks, what, meta, s);
+        return launch_lloyd_tiles((const float *)X, N, k, st, tb.box, tb.tsum, tb.tsq, lab, sc.partial.as<double>(), nblocks, what,
+                                  meta, s);
+    };
     for (double &v : sc.prune_stats) v = 0;
     OFC_TRY(launch_lloyd_set_centers(st, k, d, s, prune));
     // ---- Lloyd iterations ----
@@ -269,16 +289,12 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
             // run in the mode k_lloyd_update chose from the previous iteration's tile counts (lloyd_tiles.hip)
             const int tiles = (prune && !labelled) ? (it + w == 0 ? 1 : 2) : 0;
             if (tiles == 1) {      // is the field coherent enough? then tile metadata + column sums of squares, then iteration 0
-                OFC_TRY(launch_lloyd_tiles((const float *)X, N, k, st, nullptr, nullptr, nullptr, nullptr,
-                                           sc.partial.as<double>(), nblocks, LLOYD_WHAT_PROBE, nullptr, s));
-                OFC_TRY(launch_lloyd_tiles((const float *)X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, nullptr,
-                                           sc.partial.as<double>(), nblocks, LLOYD_WHAT_META, nullptr, s));
+                OFC_TRY(tiles_launch(nullptr, LLOYD_WHAT_PROBE, nullptr));
+                OFC_TRY(tiles_launch(nullptr, LLOYD_WHAT_META, nullptr));
                 OFC_TRY(launch_reduce_records(sc.partial.as<double>(), nblocks, 2, sc.tile_meta.as<double>(), s));
             }
             if (tiles)
-                OFC_TRY(launch_lloyd_tiles((const float *)X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, nullptr,
-                                           sc.partial.as<double>(), nblocks, LLOYD_WHAT_SWEEP,
-                                           tiles == 1 ? sc.tile_meta.as<double>() : nullptr, s));
+                OFC_TRY(tiles_launch(nullptr, LLOYD_WHAT_SWEEP, tiles == 1 ? sc.tile_meta.as<double>() : nullptr));
             else if (wdev)
                 OFC_TRY(launch_lloyd_assign_w(X, dtype, wdev, w_dtype, N, d, k, st, labels_dev, sc.partial.as<double>(),
                                               nblocks, labelled ? 1 : 3, it + w == 0, s));
@@ -341,8 +357,7 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
     const bool final_tiles = !strict && prune && !labelled && tiles_next == LLOYD_TILES_PRUNED;
     sc.prune_stats[5] = final_tiles ? 1 : 0;
     if (final_tiles)                        // the fit's tile metadata is valid and most tiles pass: those are not read
-        OFC_TRY(launch_lloyd_tiles((const float *)X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, labels_dev,
-                                   sc.partial.as<double>(), nblocks, LLOYD_WHAT_FINAL, nullptr, s));
+        OFC_TRY(tiles_launch(labels_dev, LLOYD_WHAT_FINAL, nullptr));
     else if (!strict && wdev)
         OFC_TRY(launch_lloyd_assign_w(X, dtype, wdev, w_dtype, N, d, k, st, labels_dev, sc.partial.as<double>(), nblocks, 2, 0, s));
     else if (!strict)
@@ -383,6 +398,30 @@ static int lloyd_predict_dev(int device, const void *X, int dtype, int64_t N, in
     return OFC_OK;
 }
 
+// the measurement hooks: two untimed launches, then the average of `iters` by HIP events on the stream; the events are
+// destroyed whichever way it ends
+template <class F> static int time_launches(hipStream_t s, int iters, F &&launch, float *ms_per_launch)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto timed = [&]() -> int {
+        OFC_HIP(hipEventCreate(&e0));
+        OFC_HIP(hipEventCreate(&e1));
+        for (int w = 0; w < 2; w++) OFC_TRY(launch());
+        OFC_HIP(hipEventRecord(e0, s));
+        for (int i = 0; i < iters; i++) OFC_TRY(launch());
+        OFC_HIP(hipEventRecord(e1, s));
+        OFC_HIP(hipEventSynchronize(e1));
+        float ms = 0;
+        OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
+        *ms_per_launch = ms / iters;
+        return OFC_OK;
+    };
+    const int rc = timed();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
+}
+
 static void widen_labels(const uint8_t *src, int64_t N, int32_t *dst)
 {
     for (int64_t i = 0; i < N; i++) dst[i] = src[i];
@@ -414,12 +453,8 @@ int ofc_bench_lloyd_sweep(int device, const float *X_dev, int64_t N, int k, cons
     OFC_TRY(sc.init());
     hipStream_t s = sc.stream;
     const int nblocks = lloyd_grid(N);
-    const size_t need = (size_t)(N >> 6) * 16;
-    if (sc.tile_box.bytes < need) {
-        OFC_TRY(sc.tile_box.alloc(need));
-        OFC_TRY(sc.tile_sum.alloc(need));
-        OFC_TRY(sc.tile_sq.alloc(need / 2));
-    }
+    LloydFieldBufs tb = {};
+    OFC_TRY(sc.tile_bufs(N, 0, tb));
     if (sc.labels.bytes < (size_t)N) OFC_TRY(sc.labels.alloc((size_t)N));
     LloydState *st = sc.state.as<LloydState>();
     OFC_HIP(hipMemsetAsync(st, 0, sizeof(LloydState), s));
@@ -433,31 +468,18 @@ int ofc_bench_lloyd_sweep(int device, const float *X_dev, int64_t N, int k, cons
     auto launch = [&]() -> int {
         switch (what) {
         case 0: return launch_lloyd_assign(X, OFC_F32, N, 2, k, st, sc.labels.as<uint8_t>(), partial, nblocks, 3, 0, s);
-        case 1: case 5: return launch_lloyd_tiles(X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, nullptr, partial, nblocks, LLOYD_WHAT_SWEEP, nullptr, s);
-        case 2: return launch_lloyd_tiles(X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, nullptr, partial, nblocks, LLOYD_WHAT_META, nullptr, s);
+        case 1: case 5: return launch_lloyd_tiles(X, N, k, st, tb.box, tb.tsum, tb.tsq, nullptr, partial, nblocks, LLOYD_WHAT_SWEEP, nullptr, s);
+        case 2: return launch_lloyd_tiles(X, N, k, st, tb.box, tb.tsum, tb.tsq, nullptr, partial, nblocks, LLOYD_WHAT_META, nullptr, s);
         case 3: return launch_lloyd_assign(X, OFC_F32, N, 2, k, st, sc.labels.as<uint8_t>(), partial, nblocks, 2, 0, s);
-        default: return launch_lloyd_tiles(X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, sc.labels.as<uint8_t>(), partial, nblocks, LLOYD_WHAT_FINAL, nullptr, s);
+        default: return launch_lloyd_tiles(X, N, k, st, tb.box, tb.tsum, tb.tsq, sc.labels.as<uint8_t>(), partial, nblocks, LLOYD_WHAT_FINAL, nullptr, s);
         }
     };
     if (what == 1 || what == 4 || what == 5) {      // the pruned sweeps need the tile metadata and the mode flag
-        OFC_TRY(launch_lloyd_tiles(X, N, k, st, sc.tile_box.p, sc.tile_sum.p, sc.tile_sq.p, nullptr, partial, nblocks, LLOYD_WHAT_META, nullptr, s));
+        OFC_TRY(launch_lloyd_tiles(X, N, k, st, tb.box, tb.tsum, tb.tsq, nullptr, partial, nblocks, LLOYD_WHAT_META, nullptr, s));
         const int mode = what == 5 ? LLOYD_TILES_FULL : LLOYD_TILES_PRUNED;
         OFC_HIP(hipMemcpyAsync(&st->prune_mode, &mode, sizeof(int), hipMemcpyHostToDevice, s));
     }
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
-    for (int w = 0; w < 2; w++) OFC_TRY(launch());
-    OFC_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; i++) OFC_TRY(launch());
-    OFC_HIP(hipEventRecord(e1, s));
-    OFC_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return OFC_OK;
+    return time_launches(s, iters, launch, ms_per_launch);
 }
 
 /* see include/ofc.h */
@@ -476,6 +498,43 @@ int ofc_kmeans_fit_dev_stats(int device, const void *X_dev, int dtype, int64_t N
                              double *inertia, int *n_iter)
 {
     return lloyd_fit_dev(device, X_dev, dtype, N, d, k, init, max_iter, tol_rel, centers, labels_dev, inertia, n_iter, colsum);
+}
+
+/* see include/ofc.h */
+int ofc_kmeans_fit_dev_field(int device, const void *X_dev, int dtype, int64_t N, int d, int k, const double *init,
+                             int max_iter, double tol_rel, const double *colsum, double *centers, uint8_t *labels_dev,
+                             double *inertia, int *n_iter, int W, int H, int64_t n_fields)
+{
+    OFC_REQUIRE(dtype == OFC_F32 && d == 2, "a stack of (u,v) fields is float32 with d = 2 (got dtype %d, d = %d)", dtype, d);
+    OFC_REQUIRE(W >= 1 && H >= 1 && n_fields >= 1 && N / W / H == n_fields && n_fields * W * H == N,
+                "N=%lld is not %lld fields of %d x %d", (long long)N, (long long)n_fields, W, H);
+    return lloyd_fit_dev(device, X_dev, dtype, N, d, k, init, max_iter, tol_rel, centers, labels_dev, inertia, n_iter, colsum,
+                         nullptr, OFC_F32, W, H, n_fields);
+}
+
+/* see include/ofc.h */
+int64_t ofc_lloyd_field_origin(int64_t tile, int quad, int W)
+{
+    if (tile < 0 || quad < 0 || quad > 15 || W < FIELD_GW || W % FIELD_GW) return -1;
+    return field_quad_origin(tile, quad, W);
+}
+
+/* see include/ofc.h */
+int ofc_lloyd_field_origins(int64_t tile0, int64_t n_tiles, int W, int64_t *out)
+{
+    OFC_REQUIRE(out && tile0 >= 0 && n_tiles >= 0 && W >= FIELD_GW && W % FIELD_GW == 0, "bad arguments");
+    for (int64_t i = 0; i < n_tiles; i++)
+        for (int q = 0; q < 16; q++) out[i * 16 + q] = field_quad_origin(tile0 + i, q, W);
+    return OFC_OK;
+}
+
+/* see include/ofc.h */
+void ofc_lloyd_field_shape(int *tile_w, int *tile_h, int *group_w, int *group_h)
+{
+    if (tile_w) *tile_w = FIELD_TW;
+    if (tile_h) *tile_h = FIELD_TH;
+    if (group_w) *group_w = FIELD_GW;
+    if (group_h) *group_h = FIELD_GH;
 }
 
 // ---- host-driven building blocks ----
@@ -1234,20 +1293,7 @@ int ofc_bench_lloyd_sweep_w(int device, const float *X_dev, const void *w_dev, i
     auto launch = [&]() -> int {
         return launch_lloyd_assign_w(X_dev, OFC_F32, w_dev, w_dtype, N, 2, k, st, nullptr, sc.partial.as<double>(), nblocks, 3, 0, s);
     };
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
-    for (int w = 0; w < 2; w++) OFC_TRY(launch());
-    OFC_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; i++) OFC_TRY(launch());
-    OFC_HIP(hipEventRecord(e1, s));
-    OFC_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return OFC_OK;
+    return time_launches(s, iters, launch, ms_per_launch);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // lloyd_common.h -- device-side state and launcher prototypes of the Lloyd kernels.
 #pragma once
 #include "ofc_common.h"
+#include "lloyd_field.h"
 
 #include <cmath>
 
@@ -73,6 +74,14 @@ enum { LLOYD_WHAT_SWEEP = 0, LLOYD_WHAT_META = 1, LLOYD_WHAT_FINAL = 2, LLOYD_WH
 bool lloyd_tiles_supported(int dtype, int d, int k);
 int launch_lloyd_tiles(const float *X, int64_t N, int k, const LloydState *st, void *box, void *tsum, void *tsq,
                        uint8_t *labels, double *partial, int nblocks, int what, const double *meta, hipStream_t s);
+// The same four launches over a stack of fields of width W cut into 2-D tiles under 64 x 8-pixel groups (lloyd_field.h;
+// N a multiple of 8 W).  Tile records as above but group-major, N/64 of each; group records gbox / gsum / gsq, N/512 of each.
+struct LloydFieldBufs {
+    void *box, *tsum, *tsq, *gbox, *gsum, *gsq;
+    int W;
+};
+int launch_lloyd_tiles_field(const float *X, int64_t N, int k, const LloydState *st, const LloydFieldBufs &f, uint8_t *labels,
+                             double *partial, int nblocks, int what, const double *meta, hipStream_t s);
 // tiles: 0 = the sweep was not a k_lloyd_tiles one, otherwise it ran in st->prune_mode (1: iteration 0)
 int launch_lloyd_update(LloydState *st, const double *tot, int k, int d, int after_reloc, int labelled, int first,
                         double n_total, double tol_rel, LloydStatus *status, hipStream_t s, int tiles = 0);

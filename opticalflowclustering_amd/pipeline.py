@@ -237,7 +237,7 @@ class ClipPipeline:
                                           colsum=colsum, n_global=n_global)
         self._label_k = None
         fit = kmeans_fit_dev(self.flows.ptr, _lib.F32, N, 2, init, max_iter, tol, self.labels.ptr, self.device, colsum=colsum,
-                             weights_ptr=wptr, weight_dtype=_lib.F32)
+                             weights_ptr=wptr, weight_dtype=_lib.F32, field=(self.W, self.H))
         self._label_k = len(fit[0])
         return fit
 

@@ -1,5 +1,7 @@
 """Lloyd over the full bench clip's (u,v) field with and without the tile sweeps (csrc/lloyd_tiles.hip): time per fit,
-iterations, centres, share of tiles skipped.  usage: python tools/lloyd_prune_bench.py [frames]"""
+iterations, centres, share of tiles skipped.  usage: python tools/lloyd_prune_bench.py [frames] [--field]
+--field: only the fit as ClipPipeline.run_kmeans runs it (2-D tiles under 64 x 8 groups, the fit knows the field's size)
+against the same fit over 64 x 1 tiles (the call without the size), alternating, OFC_LLOYD_PRUNE as set (default auto)."""
 import os
 import sys
 import time
@@ -12,11 +14,35 @@ from opticalflowclustering_amd import _lib
 from opticalflowclustering_amd.cluster import prune_stats
 from opticalflowclustering_amd.pipeline import ClipPipeline
 
-T = int(sys.argv[1]) if len(sys.argv) > 1 else 300
+FIELD = "--field" in sys.argv
+ARGS = [a for a in sys.argv[1:] if a != "--field"]
+T = int(ARGS[0]) if ARGS else 300
 pipe = ClipPipeline(1920, 1080, T, batch_pairs=auto_batch(T - 1), n_engines=2)
 pipe.synth(0)
 pipe.run_flow()
 lib = _lib.load()
+if FIELD:
+    from opticalflowclustering_amd.cluster import kmeans_fit_dev
+    N, colsum, out = pipe.n_pairs * pipe.W * pipe.H, pipe._colsum(), {}
+    for form in ("1d", "field", "1d", "field", "1d", "field"):
+        kw = dict(labels_ptr=pipe.labels.ptr, colsum=colsum, field=(pipe.W, pipe.H) if form == "field" else None)
+        kmeans_fit_dev(pipe.flows.ptr, _lib.F32, N, 2, INIT, **kw)
+        _lib.check(lib.ofc_device_sync(0))
+        t0 = time.perf_counter()
+        for _ in range(5):
+            cen, inertia, n_iter = kmeans_fit_dev(pipe.flows.ptr, _lib.F32, N, 2, INIT, **kw)
+        _lib.check(lib.ofc_device_sync(0))
+        ms = (time.perf_counter() - t0) / 5 * 1e3
+        lab = pipe.labels_host()
+        print("%-5s tiles: %.3f ms per fit, n_iter %d, inertia %.10e, %s" % (form, ms, n_iter, inertia, prune_stats()), flush=True)
+        if form in out:
+            assert np.array_equal(out[form][0], cen) and np.array_equal(out[form][1], lab), "not reproducible"
+        out[form] = (cen, lab, n_iter, inertia)
+    a, b = out["field"], out["1d"]
+    print("field vs 1d: max centre diff %.3e, labels equal %s, n_iter %d / %d, inertia rel diff %.2e" % (
+        np.abs(a[0] - b[0]).max(), np.array_equal(a[1], b[1]), a[2], b[2], abs(a[3] - b[3]) / b[3]))
+    pipe.close()
+    sys.exit(0)
 res = {}
 for policy in ("0", "1", "3", "0", "1"):
     os.environ["OFC_LLOYD_PRUNE"] = policy
