@@ -825,6 +825,67 @@ int ofc_frames_reverse_dev(int device, const uint8_t *frames_dev, int W, int H, 
 int ofc_bench_consist(int device, const float *fwd_dev, const float *bwd_dev, int W, int H, int npair, int what, int iters,
                       float *ms_per_run);
 
+/* ---- Photometric consistency: which vectors of a field carry a pixel of frame t onto a like grey value of frame t+1
+ * (brightness constancy).  It needs no backward field, only the u8 frames the field was computed from, so it also exists on
+ * a stream; it says little where the image has no texture, so it complements the forward-backward check and does not
+ * replace it.  The reference has no counterpart: it trusted every vector of cv2.calcOpticalFlowFarneback alike
+ * (computeOpticalFlowModule.py:20-22).
+ * Definition (normative, like the text above; every output is an integer).
+ * Inputs: frames u8 [npair+1][H][W]; pair t is I0 = frames[t], I1 = frames[t+1].  fwd f32 [npair][H][W][2], pair t on frame
+ * t's grid.
+ * Quantisation and landing are exactly the forward-backward check's: Q(u) = llrint((double)u * 65536); a vector is valid
+ * iff u, v are finite and |u|, |v| < 1024; X = x*65536 + Q(u), Y = y*65536 + Q(v); the pixel lands inside iff
+ * 0 <= X <= (W-1) << 16 and 0 <= Y <= (H-1) << 16.  ix = X >> 16, fx = X & 65535, iy and fy likewise.  The four taps are
+ * (ix, iy), (min(ix+1, W-1), iy), (ix, min(iy+1, H-1)), (min(ix+1, W-1), min(iy+1, H-1)) with the weights
+ * (65536-fx)(65536-fy), fx(65536-fy), (65536-fx)fy, fx*fy (they sum to 2^32).
+ * Warped intensity: S = sum of w_i * I1(tap_i) in 64-bit integers, 0 <= S <= 255 * 2^32 < 2^40; J = (S + 2^23) >> 24, in
+ * 0 .. 65280: the grey value in 1/256 levels.  An implementation may form S as top*(65536-fy) + bot*fy with
+ * top = I00*(65536-fx) + I10*fx < 2^24: that is the same integer.  No intermediate may be rounded.
+ * Residual and contrast: e = J - 256 * I0(x, y); c = max - min of the four tap values of I1, in 0 .. 255.  A tap of weight
+ * zero counts: nothing may depend on a fraction being exactly 0.
+ * Verdict: consistent iff |e| <= tau_q + kappa_q * c, with tau_q in 0 .. 65280 (1/256 grey levels) and kappa_q in 0 .. 1024
+ * (1/256 grey levels of residual per grey level of local contrast: it forgives the sub-pixel error of a vector that sits on
+ * an edge).  Everything fits int32.
+ * Outputs: state u8 [npair][H][W] with the forward-backward check's codes OFC_CONSIST_*, decided in this order: the forward
+ * vector is invalid -> INVALID (3); the pixel lands outside -> LEAVES (2); else the comparison, OK (0) or MISMATCH (1).
+ * stats int64 [npair][5]: the pixels of the pair in each of the four states, then the sum of |e| over the pixels of states 0
+ * and 1 (below 2^44).  Optionally warped u16 [npair][H][W]: J for the states 0 and 1, and 0 otherwise.
+ * Limits: W, H in 1 .. 16384 (above: OFC_EUNSUPPORTED; below 1: OFC_EINVAL); npair in 1 .. 65535, tau_q and kappa_q in their
+ * ranges (otherwise OFC_EINVAL). ---- */
+#define OFC_PHOTO_SHARE 2048     /* consecutive pixels of a pair a work-group of the check kernel takes */
+#define OFC_PHOTO_TAU_MAX 65280
+#define OFC_PHOTO_KAPPA_MAX 1024
+#define OFC_PHOTO_NSTAT 5
+/* Host only, no device is touched: OFC_OK iff the arguments are inside the limits above.  Every call below decides by it
+ * before anything is allocated or launched.  No counterpart in the reference, as for every call of this block. */
+int ofc_photo_check(int W, int H, int npair, int tau_q, int kappa_q);
+/* frames_dev u8 [npair+1][H][W], fwd_dev f32 [npair][H][W][2] (8-byte aligned; read with 16-byte loads where every pair's
+ * base allows) -> state_dev u8 [npair][H][W], stats_dev int64 [npair][5] (8-byte aligned; cleared here), and warped_dev u16
+ * [npair][H][W] (2-byte aligned) unless it is NULL.  Every tap index is clamped into the frame before it indexes anything,
+ * whatever the field holds.  Neither input is written.  Returns when done.  No counterpart in the reference. */
+int ofc_photo_dev(int device, const uint8_t *frames_dev, const float *fwd_dev, int W, int H, int npair, int tau_q, int kappa_q,
+                  uint8_t *state_dev, int64_t *stats_dev, uint16_t *warped_dev);
+/* The whole chain on host buffers of the same shapes; warped_host may be NULL.  No counterpart in the reference. */
+int ofc_photo(int device, const uint8_t *frames_host, const float *fwd_host, int W, int H, int npair, int tau_q, int kappa_q,
+              uint8_t *state_host, int64_t *stats_host, uint16_t *warped_host);
+/* Measurement hook: average duration by HIP events over `iters` runs, two warm-up runs before them, on frames_dev and
+ * fwd_dev (tau_q 2048, kappa_q 128) with outputs of the hook's own, the clear of the stats included.  what = 0: the check
+ * alone; 1: the check with `warped`.  No counterpart in the reference. */
+int ofc_bench_photo(int device, const uint8_t *frames_dev, const float *fwd_dev, int W, int H, int npair, int what, int iters,
+                    float *ms_per_run);
+/* A stream that checks its vectors photometrically: from the next batch on, every pair of a batch is checked against the
+ * slot's own frames directly behind the flow and BEFORE the camera (if any) is fitted and subtracted (a residual does not
+ * say where a pixel lands: the rule the link moves follow); the stats go to a row per pair.  On a stream with blobs every
+ * pixel whose state is not in `keep` (a set of states as for ofc_consist_mask_dev, 1 .. 15) becomes background of the key map
+ * before the components are found; the links' moves are left alone.  on = 0 removes the check: the stream then launches
+ * exactly what a stream that never had one launches.  Same precondition as ofc_stream_set_blobs (no frame and no
+ * undelivered result; otherwise OFC_EINVAL and nothing changes); tau_q, kappa_q as ofc_photo_check decides them for the
+ * stream's frame size.  No counterpart in the reference. */
+int ofc_stream_set_photo(ofc_stream_t *s, int on, int tau_q, int kappa_q, int keep);
+/* The stats [n][5] of the n pairs the LAST finish delivered.  Valid under ofc_stream_read_blobs' conditions; max_pairs < n:
+ * OFC_EINVAL, nothing written; OFC_EINVAL without the check.  No counterpart in the reference. */
+int ofc_stream_read_photo(ofc_stream_t *s, int64_t *stats_host, int max_pairs);
+
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.

@@ -21,6 +21,7 @@ BLOB_LINK_FIELDS, BLOB_NO_MOVE = 3, -0x7fff8000      # OFC_BLOB_LINK_FIELDS; OFC
 CONSIST_OK, CONSIST_MISMATCH, CONSIST_LEAVES, CONSIST_INVALID, CONSIST_STATES = 0, 1, 2, 3, 4   # OFC_CONSIST_*
 CONSIST_SHARE, CONSIST_MAX_DIM = 2048, 16384         # OFC_CONSIST_SHARE, OFC_CONSIST_MAX_DIM
 CONSIST_ALPHA_MAX, CONSIST_BETA_MAX = 65536, 1 << 62  # OFC_CONSIST_ALPHA_MAX, OFC_CONSIST_BETA_MAX
+PHOTO_SHARE, PHOTO_TAU_MAX, PHOTO_KAPPA_MAX, PHOTO_NSTAT = 2048, 65280, 1024, 5      # OFC_PHOTO_*
 
 
 class OfcError(RuntimeError):
@@ -167,6 +168,12 @@ _PROTOS = {
     "ofc_consist_mask_dev": ([_i, _vp, _i64, _i, _vp, _vp], _i),
     "ofc_frames_reverse_dev": ([_i, _vp, _i, _i, _i, _vp], _i),
     "ofc_bench_consist": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
+    "ofc_photo_check": ([_i, _i, _i, _i, _i], _i),
+    "ofc_photo_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "ofc_photo": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "ofc_bench_photo": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
+    "ofc_stream_set_photo": ([_vp, _i, _i, _i, _i], _i),
+    "ofc_stream_read_photo": ([_vp, _vp, _i], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

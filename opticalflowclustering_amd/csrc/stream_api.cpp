@@ -10,10 +10,14 @@
 // With blob links (ofc_stream_set_blob_links) the batch's moves are taken from the field before the camera is subtracted,
 // and behind the blobs every transition between consecutive pairs is voted (blob_links.hip): those inside the batch, and
 // the one from the previous batch's last pair, whose label map, moves and areas the stream carries over.
+// With a photometric check (ofc_stream_set_photo) every pair's vectors are checked against the slot's own frames directly
+// behind the flow, before the camera is subtracted (photo_check.hip); with blobs the key map is masked by the check's states.
 #include "blob_links.h"
 #include "color_common.h"
+#include "fb_check.h"
 #include "lloyd_common.h"
 #include "motion_model.h"
+#include "photo_check.h"
 
 #include <memory>
 
@@ -64,6 +68,13 @@ struct ofc_stream {
     DevBuf link_carry;                 // the previous batch's last pair: label map, moves, areas, int32 [3][H][W]
     DevBuf link_keys, link_votes, link_counters;   // [max_pairs][cap] uint64, [max_pairs][cap] int32, [max_pairs] int32: grow
     size_t link_cap = 0;               // transitions
+    // the photometric check, when there is one (photo_on): every pair's stats, kept past the finish like the camera's fits
+    bool photo_on = false;
+    int photo_tau = 0, photo_kappa = 0, photo_keep = 0;
+    DevBuf photo_state;                // one batch's state map, u8 [batch][H][W]
+    DevBuf photo_stats;                // [max_pairs][5] int64: grows with `cells`
+    size_t photo_cap = 0;              // pairs
+    int photo_pairs = 0;               // pairs of the last finish: what ofc_stream_read_photo delivers
 };
 
 namespace {
@@ -174,6 +185,24 @@ int ensure_links(ofc_stream *s, int need_pairs)
     return OFC_OK;
 }
 
+// room for the photometric stats of need_pairs pairs: same growth as ensure_camera, what was checked so far is kept
+int ensure_photo(ofc_stream *s, int need_pairs)
+{
+    if ((size_t)need_pairs <= s->photo_cap) return OFC_OK;
+    const size_t cap = std::max<size_t>(need_pairs, s->photo_cap ? s->photo_cap * 2 : 256);
+    const size_t per = sizeof(int64_t) * PHOTO_NSTAT;
+    DevBuf nb;
+    OFC_TRY(nb.alloc(cap * per));
+    if (s->photo_stats.p && s->pairs_submitted) {
+        OFC_HIP(hipStreamSynchronize(s->compute));
+        OFC_HIP(hipMemcpy(nb.p, s->photo_stats.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
+    }
+    std::swap(s->photo_stats.p, nb.p);
+    std::swap(s->photo_stats.bytes, nb.bytes);
+    s->photo_cap = cap;
+    return OFC_OK;
+}
+
 // Behind a batch's label maps: its areas, then the votes of the transition from the carried pair (when the clip has one
 // before this batch) and of the batch's inner transitions; then the batch's last pair becomes the carried one.
 int submit_links(ofc_stream *s, const int32_t *labels, int npair)
@@ -210,10 +239,16 @@ int submit(ofc_stream *s, int i)
     if (s->cam_kind) OFC_TRY(ensure_camera(s, s->pairs_submitted + npair));
     if (s->blob_conn) OFC_TRY(ensure_blobs(s, s->pairs_submitted + npair));
     if (s->link_max) OFC_TRY(ensure_links(s, s->pairs_submitted + npair));
+    if (s->photo_on) OFC_TRY(ensure_photo(s, s->pairs_submitted + npair));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
     OFC_TRY(ofc_flow_calc_frames_dev(s->flow, sl.frames.as<uint8_t>(), sl.n_frames, sl.flows.as<float>()));
+    // the photometric check follows the whole flow into the slot's own next frame: before the camera is subtracted
+    if (s->photo_on)
+        OFC_TRY(launch_photo_check(sl.frames.as<uint8_t>(), sl.flows.as<float>(), s->W, s->H, npair, s->photo_tau, s->photo_kappa,
+                                   s->photo_state.as<uint8_t>(),
+                                   s->photo_stats.as<int64_t>() + (size_t)s->pairs_submitted * PHOTO_NSTAT, nullptr, s->compute));
     // where the pixels go is what the whole flow says: the moves are taken before the camera is subtracted
     if (s->link_max) OFC_TRY(launch_blob_moves(sl.flows.as<float>(), s->W, s->H, npair, s->link_moves.as<int32_t>(), s->compute));
     if (s->cam_kind) {
@@ -240,6 +275,9 @@ int submit(ofc_stream *s, int i)
         int *err = s->blob_err.as<int>();
         OFC_TRY(launch_blob_keys(sl.flows.as<float>(), s->W, s->H, npair, true, s->blob_thr, s->k ? s->model.as<LloydState>() : nullptr,
                                  s->k, (1u << s->k) - 1u, false, keys, s->compute));
+        // a pixel whose vector failed the photometric check belongs to no blob
+        if (s->photo_on)
+            OFC_TRY(launch_consist_mask(s->photo_state.as<uint8_t>(), (int64_t)P * npair, s->photo_keep, keys, nullptr, s->compute));
         OFC_TRY(launch_blob_local(keys, s->W, s->H, npair, s->blob_conn, labels, err, s->compute));
         OFC_TRY(launch_blob_seam(keys, s->W, s->H, npair, s->blob_conn, labels, err, s->compute));
         OFC_TRY(launch_blob_flatten(s->W, s->H, npair, labels, err, s->compute));
@@ -348,6 +386,7 @@ int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pai
     }
     s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
     s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
+    s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -398,6 +437,7 @@ int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts,
     }
     s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
     s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
+    s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -586,6 +626,49 @@ int ofc_stream_read_blob_links(ofc_stream_t *s, int64_t *links_host, int32_t *nl
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
     return blob_links_read(s->link_keys.as<uint64_t>(), s->link_votes.as<int32_t>(), s->link_counters.as<int32_t>(), ntrans,
                            s->link_max, links_host, nlinks_host);
+}
+
+int ofc_stream_set_photo(ofc_stream_t *s, int on, int tau_q, int kappa_q, int keep)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (on != 0) {
+        OFC_TRY(photo_check(s->W, s->H, s->batch, tau_q, kappa_q));
+        OFC_REQUIRE(keep >= 1 && keep < (1 << FB_NSTATE), "keep = %d: a set of the four states, 1 .. 15", keep);
+    }
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: set the photometric check on a fresh stream or straight after a "
+                "finish");
+    OFC_TRY(ensure_device(s->device));
+    s->photo_pairs = 0;
+    if (on == 0) {
+        s->photo_state.release();
+        s->photo_stats.release();
+        s->photo_cap = 0;
+        s->photo_on = false;
+        return OFC_OK;
+    }
+    const size_t n = (size_t)s->W * s->H * s->batch;
+    if (s->photo_state.bytes < n) OFC_TRY(s->photo_state.alloc(n));
+    s->photo_on = true;
+    s->photo_tau = tau_q;
+    s->photo_kappa = kappa_q;
+    s->photo_keep = keep;
+    return OFC_OK;
+}
+
+int ofc_stream_read_photo(ofc_stream_t *s, int64_t *stats_host, int max_pairs)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->photo_on, "the stream has no photometric check (ofc_stream_set_photo)");
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: read the photometric stats straight after a finish");
+    OFC_REQUIRE(max_pairs >= s->photo_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->photo_pairs);
+    OFC_TRY(ensure_device(s->device));
+    if (!s->photo_pairs) return OFC_OK;
+    OFC_REQUIRE(stats_host, "null pointer");
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    OFC_HIP(hipMemcpy(stats_host, s->photo_stats.p, sizeof(int64_t) * PHOTO_NSTAT * (size_t)s->photo_pairs, hipMemcpyDeviceToHost));
+    return OFC_OK;
 }
 
 void ofc_stream_destroy(ofc_stream_t *s)

@@ -40,6 +40,13 @@ to the forward-backward check on the device (consistency.py), before any camera 
 every pixel that failed it, and the --blobs key map keeps only those that passed.  --fb-alpha and --fb-beta are the check's
 two constants (the literature's 0.01 and 0.5 px^2 by default, not tuned here); --fb-counts writes the (pairs, 4) pixel
 counts per state.
+
+With --photometric every vector is put to the photometric check instead (photometric.py): the next frame, read where the
+pixel lands, must show the pixel's own grey value to within --photo-tau grey levels plus --photo-kappa times the local
+contrast (8 and 0.5 by default, a convention that is not tuned here).  It needs no second flow, so it works on the resident
+route, where it does what --consistent does with its state map, and on --stream and --fit-stream, where the stream's blobs
+keep only the pixels that passed.  --photo-counts writes the (pairs, 5) stats: the pixels per state, then the sum of the
+absolute error in 1/256 grey levels.  The two checks cannot be combined.
 """
 import argparse
 import os
@@ -172,7 +179,25 @@ def parse_arguments(argv=None):
     ap.add_argument("--fb-alpha", type=float, default=0.01, help="relative term of the check (a convention, not tuned)")
     ap.add_argument("--fb-beta", type=float, default=0.5, help="absolute term of the check in px^2 (a convention, not tuned)")
     ap.add_argument("--fb-counts", metavar="FILE.npy", help="write the (pairs, 4) pixel counts per state to this .npy file")
+    ap.add_argument("--photometric", action="store_true",
+                    help="photometric check of every vector against the frames (any route): failed pixels get weight 0 on the "
+                         "resident route and no blob on every route")
+    ap.add_argument("--photo-tau", type=float, default=8.0, help="absolute term of the check in grey levels (a convention, not tuned)")
+    ap.add_argument("--photo-kappa", type=float, default=0.5,
+                    help="grey levels forgiven per grey level of local contrast (a convention, not tuned)")
+    ap.add_argument("--photo-counts", metavar="FILE.npy", help="write the (pairs, 5) stats of the check to this .npy file")
     args = ap.parse_args(argv)
+    if args.photometric:
+        if args.consistent:
+            ap.error("--photometric and --consistent each leave a state map of their own: combining the two is not supported")
+        from .photometric import quantise as photo_quantise
+        try:
+            photo_quantise(args.photo_tau, args.photo_kappa)
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.photo_counts or args.photo_tau != 8.0 or args.photo_kappa != 0.5:
+        ap.error("--photo-tau, --photo-kappa and --photo-counts belong to --photometric")
+    args.photo_spec = dict(tau=args.photo_tau, kappa=args.photo_kappa) if args.photometric else None
     if args.consistent:
         for flag, given in (("--stream", args.stream), ("--fit-stream", args.fit_stream)):
             if given:
@@ -244,11 +269,24 @@ def read_gray_frames(path, device=0):
     return np.stack(frames)
 
 
+def _save_npy(path, a):
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    np.save(path, a)
+
+
+def _print_photometric(stats, tau_q, kappa_q):
+    from .photometric import STATE_NAMES, Photometric
+    ph = Photometric(None, stats, None, tau_q, kappa_q)
+    total, compared = ph.counts.sum(), ph.counts[:, :2].sum()
+    print("photometric check: " + ", ".join(f"{100.0 * s:.2f} % {name}" for name, s in zip(STATE_NAMES, ph.counts.sum(0) / max(total, 1)))
+          + (f"; mean absolute error {ph.abs_error.sum() / (256.0 * compared):.3f} grey levels" if compared else ""))
+
+
 def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None, blobs=None, blobs_out=None,
-                  max_links=0):
+                  max_links=0, photometric=None, photo_out=None):
     """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident; camera as
     FlowStream's, its (pairs, 6) models saved to camera_out; blobs as FlowStream's, their rows written to blobs_out, with
-    max_links linked and with their track ids"""
+    max_links linked and with their track ids; photometric as FlowStream's, its (pairs, 5) stats saved to photo_out"""
     from .stream import FlowStream
     fs, n = None, 0
     if blobs is not None and max_links:
@@ -257,7 +295,7 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
         for gray in gray_frames(path, device):
             if fs is None:
                 fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, centers=centers,
-                                camera=camera, blobs=blobs)
+                                camera=camera, blobs=blobs, photometric=photometric)
             fs.push(gray)
             n += 1
         if n < 2:
@@ -267,6 +305,11 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
             np.save(camera_out, fs.camera_motion().params)
         if blobs is not None and blobs_out:
             write_blob_csv(blobs_out, fs.blobs(), tracks=bool(max_links))
+        if photometric is not None:
+            stats = fs.photometric_stats()
+            _print_photometric(stats, *fs.photo_args[:2])
+            if photo_out:
+                _save_npy(photo_out, stats)
         return counts
     finally:
         if fs is not None:
@@ -307,12 +350,12 @@ def main(argv=None):
         centers, _, _ = hist.fit(k, init="k-means++" if given is None else given, random_state=args.seed, n_init=args.n_init,
                                  device=args.device)
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out, args.blob_spec, args.blobs, args.max_links)
+                               args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts)
         return _write_outputs(args, counts, centers)
     if args.stream:
         centers = given
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out, args.blob_spec, args.blobs, args.max_links)
+                               args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts)
         return _write_outputs(args, counts, centers)
     from .pipeline import ClipPipeline
     frames = read_gray_frames(args.path, args.device)
@@ -331,6 +374,12 @@ def main(argv=None):
             if args.fb_counts:
                 os.makedirs(os.path.dirname(args.fb_counts) or ".", exist_ok=True)
                 np.save(args.fb_counts, checked.counts)
+        if args.photo_spec:                     # like the other check: before the camera is taken out
+            checked = pipe.photometric(**args.photo_spec)
+            _print_photometric(checked.stats, checked.tau_q, checked.kappa_q)
+            if args.photo_counts:
+                _save_npy(args.photo_counts, checked.stats)
+            fb = True
         if args.camera_spec:
             if args.max_links:
                 pipe.capture_moves()            # where the pixels go: before the camera is taken out of the field

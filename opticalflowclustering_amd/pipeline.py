@@ -60,7 +60,7 @@ class ClipPipeline:
         self._compensated = False           # compensate_camera() has run since the last run_flow()
         self.frames_rev = None              # run_backward_flow(): the resident frames in reverse order, n_frames * P u8
         self.flows_bwd = None               # ... and the field of that clip: pair t's backward field at n_pairs-1-t
-        self.state = None                   # consistency(): the state map of the forward-backward check, n_pairs * P u8
+        self.state = None                   # consistency() / photometric(): the state map of the check that ran last, n_pairs * P u8
 
     def synth(self, t0=0, seed=0):
         """fill the resident clip with synthetic frames t0 .. t0+n_frames-1"""
@@ -151,6 +151,40 @@ class ClipPipeline:
             self.state = None
             raise
         return cons.Consistency(self.state.download((n, H, W), np.uint8), counts, resid, alpha_q, beta_q)
+
+    def photometric(self, tau=8.0, kappa=0.5, warped=False):
+        """the photometric check of the resident field against the resident frames (photometric.py; ofc_photo_dev), in
+        chunks of at most 65535 pairs -> photometric.Photometric.  It needs no backward field.  The state map also stays on
+        the device, where consistency() leaves its own: whichever of the two ran last owns it, and blobs(consistent=True)
+        and run_kmeans / seed_kmeans(consistent=True) take it unchanged, until the next run_flow().  tau, kappa:
+        photometric.check's, a convention that is not tuned on anything here.  ValueError after compensate_camera(): a
+        residual does not say where a pixel lands (the rule consistency() has), so check before the camera is removed.
+        Rank-local: a pair depends on itself and its two frames alone."""
+        from . import photometric as photo
+        tau_q, kappa_q = photo.quantise(tau, kappa)
+        if self._compensated:
+            raise ValueError("photometric() after compensate_camera() would follow the residual, which does not say where a "
+                             "pixel lands: call it before compensate_camera()")
+        self.sync()
+        n, W, H = self.n_pairs, self.W, self.H
+        P = W * H
+        photo.check_args(W, H, min(n, 65535), tau_q, kappa_q)
+        if self.state is None:
+            self.state = DeviceBuffer(n * P, self.device)
+        stats, out = [], []
+        try:
+            for t0 in range(0, n, 65535):
+                m = min(65535, n - t0)
+                st, wd = photo.check_dev(self.frames.ptr + t0 * P, self.flows.ptr + t0 * P * 8, W, H, m, self.state.ptr + t0 * P,
+                                         tau_q, kappa_q, warped=warped, device=self.device)
+                stats.append(st)
+                out.append(wd)
+        except Exception:
+            self.state.free()
+            self.state = None
+            raise
+        return photo.Photometric(self.state.download((n, H, W), np.uint8), np.concatenate(stats),
+                                 np.concatenate(out) if warped else None, tau_q, kappa_q)
 
     def _state_ptr(self, what):
         if self.state is None:

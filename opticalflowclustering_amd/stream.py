@@ -8,7 +8,9 @@ pair's field is labelled against the centres and counted per grid cell on the de
 on such footage too: histogram().fit(k).  With a camera (camera="affine") every pair's camera motion is fitted and subtracted
 on the device straight after the flow (camera.py), and all of the above see the residual field.  With blobs
 (blobs=dict(thr=...)) every pair's moving regions are labelled and described on the device as well (blobs.py): blobs();
-with max_links among them the blobs of consecutive pairs are linked too, inside a batch and across batches (blobs.tracks)."""
+with max_links among them the blobs of consecutive pairs are linked too, inside a batch and across batches (blobs.tracks).
+With a photometric check (photometric=True or dict(tau=, kappa=, keep=)) every pair's vectors are checked against the batch's
+own frames (photometric.py): photometric_stats(), and the blobs keep only the pixels that passed."""
 import ctypes as C
 
 import numpy as np
@@ -18,7 +20,7 @@ from ._lib import FbParams, check, load, ptr
 
 class FlowStream:
     def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False,
-                 histogram=None, camera=None, blobs=None):
+                 histogram=None, camera=None, blobs=None, photometric=None):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
@@ -39,6 +41,35 @@ class FlowStream:
         self.max_links = 0                  # of the stream's blob links, 0 without them
         if blobs is not None:
             self.set_blobs(**blobs)
+        self.photo_args = None              # (tau_q, kappa_q, keep) of the stream's photometric check, or None
+        if photometric is not None and photometric is not False:
+            self.set_photometric(**({} if photometric is True else photometric))
+
+    def set_photometric(self, tau=8.0, kappa=0.5, keep=(0,), on=True):
+        """from the next batch on, put every pair's vectors to the photometric check against the batch's own frames
+        (ofc_stream_set_photo; photometric.py has the definition), directly behind the flow and before a camera is removed.
+        On a stream with blobs the pixels whose state is not in `keep` (consistency.keep_mask) belong to no blob; the cell
+        means, the model's counts, the histogram, the camera fit and the links' moves are left alone.  on=False removes the
+        check.  tau and kappa default to 8 grey levels and 0.5, a convention that is not tuned on anything here.  Only on a
+        stream that holds no frame and no undelivered result, as set_model; ValueError otherwise, and nothing changes."""
+        if not on:
+            check(load().ofc_stream_set_photo(self._h, 0, 0, 0, 0))
+            self.photo_args, self._last_pairs = None, 0
+            return
+        from .photometric import keep_mask, quantise
+        args = quantise(tau, kappa) + (keep_mask(keep),)
+        check(load().ofc_stream_set_photo(self._h, 1, *args))
+        self.photo_args, self._last_pairs = args, 0
+
+    def photometric_stats(self):
+        """-> (n, 5) int64 of the pairs the last finish() / finish_clusters() delivered (ofc_stream_read_photo): the pixels
+        in each of the four states, then the sum of |e| in 1/256 grey levels over the compared ones; photometric.Photometric
+        (None, stats, None, tau_q, kappa_q) gives the shares and the mean error.  Straight after a finish only; ValueError
+        once frames are held again, and on a stream without the check."""
+        n = self._last_pairs
+        stats = np.zeros((max(n, 1), 5), np.int64)
+        check(load().ofc_stream_read_photo(self._h, ptr(stats), max(n, 1)))
+        return stats[:n]
 
     def set_blobs(self, thr=0.5, connectivity=8, min_area=1, max_blobs=4096, max_links=0):
         """from the next batch on, find every pair's moving objects (ofc_stream_set_blobs; blobs.py has the definition):
