@@ -886,6 +886,79 @@ int ofc_stream_set_photo(ofc_stream_t *s, int on, int tau_q, int kappa_q, int ke
  * OFC_EINVAL, nothing written; OFC_EINVAL without the check.  No counterpart in the reference. */
 int ofc_stream_read_photo(ofc_stream_t *s, int64_t *stats_host, int max_pairs);
 
+/* ---- Repair of a flow field: a masked median fill of the vectors that are not trusted, and a median smoothing pass.  What
+ * the two checks above flag can so far only be thrown away; here a flagged vector is replaced by the component-wise median
+ * of the trusted vectors around it, round after round, until the hole is closed.  A median only selects, so every result is
+ * exact and does not depend on the order of the work.  The reference has no counterpart: it trusted every vector of
+ * cv2.calcOpticalFlowFarneback alike (computeOpticalFlowModule.py:20-22).
+ * Definition (normative, like the text above).
+ * Inputs: flow f32 [npair][H][W][2]; state u8 [npair][H][W] or NULL; keep, a set of states as for ofc_consist_mask_dev (bit
+ * s = state s), 1 .. 15; radius r in {1, 2}: a window of 3x3 or 5x5; rounds in 0 .. 254; min_count in 1 .. (2r+1)^2; smooth
+ * in {0, 1}; rounds == 0 && smooth == 0 is refused.
+ * Sources and targets: a vector is valid exactly as everywhere else: u, v finite and |u|, |v| < 1024.  Pixel p is a source
+ * iff its vector is valid and either state is NULL or bit state[p] of keep is set (a state byte above 3 is in no set).
+ * Every other pixel is a target.  V_0 is the set of sources, F_0 the input field.
+ * Round g = 1 .. rounds (Jacobi: a round reads only the snapshot F_(g-1), V_(g-1)): for every pixel p not in V_(g-1), let N
+ * be the pixels q with |qx - px| <= r and |qy - py| <= r that lie inside the frame and in V_(g-1); the window is clipped at
+ * the border, nothing is reflected, and pairs never see one another.  If |N| >= min_count: F_g[p].u is the lower median of
+ * {F_(g-1)[q].u : q in N}, the element of index floor((|N| - 1) / 2) in ascending order; F_g[p].v likewise over the v
+ * components, chosen independently of u; p joins V_g; filled[p] = g.  Everything else is carried over unchanged.
+ * Smoothing, if smooth is set, runs after the last round: for every p in V_rounds the output is the lower median, per
+ * component, over the window's pixels in V_rounds (p itself always among them), read from the snapshot F_rounds; min_count
+ * does not apply; pixels outside V_rounds and the filled map are not touched by it.
+ * Outputs: out f32 of flow's shape.  A source when smooth is 0, and a target that was never filled always, are copied bit
+ * for bit from the input.  A filled or smoothed component equals, as a number, one of the input components of its pair;
+ * which sign a zero carries is not promised (compare with ==, not by bytes).  filled u8 [npair][H][W], optional: 0 for a
+ * source, g for a target filled in round g, 255 for a target never filled.  counts int64 [npair][3]: sources, filled,
+ * unfilled; they sum to W*H.  state_out u8 [npair][H][W], optional, may be the same buffer as state: the input state
+ * carried over, filled targets become OFC_CONSIST_OK; it is written only once nothing reads state any more; with state NULL
+ * it must be NULL.
+ * Aliasing: out may be the same buffer as flow (in place), otherwise the two must not overlap.  The library owns the
+ * scratch of the snapshots and works through the pairs in chunks, so that scratch does not grow with npair.
+ * Limits: W, H in 1 .. 16384 (above: OFC_EUNSUPPORTED); npair in 1 .. 65535; anything else outside the ranges above:
+ * OFC_EINVAL.
+ * Safety: no index is formed from data; every neighbour index is clamped or predicated into the frame; no loop has a
+ * data-dependent trip count. ---- */
+#define OFC_REPAIR_TILE_W 64      /* the pixels of a frame a work-group of the sweep kernel takes: what ofc_repair_tile says */
+#define OFC_REPAIR_TILE_H 16
+#define OFC_REPAIR_ROUNDS_MAX 254
+#define OFC_REPAIR_NCOUNT 3
+#define OFC_REPAIR_UNFILLED 255   /* filled[p] of a target that no round filled */
+/* Host only, no device is touched: OFC_OK iff the arguments are inside the limits above.  Every call below decides by it
+ * before anything is allocated or launched.  No counterpart in the reference, as for every call of this block. */
+int ofc_repair_check(int W, int H, int npair, int keep, int radius, int rounds, int min_count, int smooth);
+/* Host only: out[0], out[1] = the width and height of the tile of a frame that one work-group of the sweep kernel takes at
+ * this radius, so that a test can place holes on its seams. */
+void ofc_repair_tile(int radius, int out[2]);
+/* flow_dev f32 [npair][H][W][2] (8-byte aligned; read with 16-byte loads where W is even and the base allows), state_dev u8
+ * [npair][H][W] or NULL -> out_dev of flow's shape (8-byte aligned; flow_dev itself, or disjoint from it), counts_dev int64
+ * [npair][3] (8-byte aligned; cleared here), and filled_dev, state_out_dev u8 [npair][H][W] unless they are NULL
+ * (state_out_dev may be state_dev).  rounds + smooth sweeps over the field, in scratch of the library's own.  Returns when
+ * done. */
+int ofc_repair_dev(int device, const float *flow_dev, const uint8_t *state_dev, int W, int H, int npair, int keep, int radius,
+                   int rounds, int min_count, int smooth, float *out_dev, uint8_t *filled_dev, uint8_t *state_out_dev,
+                   int64_t *counts_dev);
+/* The whole chain on host buffers of the same shapes; state_host, filled_host and state_out_host may be NULL. */
+int ofc_repair(int device, const float *flow_host, const uint8_t *state_host, int W, int H, int npair, int keep, int radius,
+               int rounds, int min_count, int smooth, float *out_host, uint8_t *filled_host, uint8_t *state_out_host,
+               int64_t *counts_host);
+/* Measurement hook: average duration by HIP events over `iters` runs, two warm-up runs before them, on flow_dev and
+ * state_dev (may be NULL; keep = {0}, min_count 1) with outputs of the hook's own, the clear of the counts included.
+ * what = 0: one fill round, r = 1; 1: one smoothing pass, r = 1; 2: one smoothing pass, r = 2. */
+int ofc_bench_repair(int device, const float *flow_dev, const uint8_t *state_dev, int W, int H, int npair, int what, int iters,
+                     float *ms_per_run);
+/* A stream that repairs its vectors: from the next batch on, every batch's field is repaired in place directly behind the
+ * photometric check, whose state map it takes and updates (filled pixels become OFC_CONSIST_OK, so on a stream with blobs
+ * they belong to blobs again and pixels that stayed unfilled do not); without a photometric check state is NULL and only
+ * invalid vectors are targets.  It runs before the link moves are taken and before the camera is fitted (a repaired vector
+ * says where a pixel lands), so everything downstream sees the repaired field.  The counts go to a row per pair.  on = 0
+ * removes it: the stream then launches exactly what a stream that never had one launches.  Preconditions exactly as
+ * ofc_stream_set_photo; the arguments as ofc_repair_check decides them for the stream's frame size. */
+int ofc_stream_set_repair(ofc_stream_t *s, int on, int keep, int radius, int rounds, int min_count, int smooth);
+/* The counts [n][3] of the n pairs the LAST finish delivered.  Valid under ofc_stream_read_photo's conditions; max_pairs < n:
+ * OFC_EINVAL, nothing written; OFC_EINVAL without the repair. */
+int ofc_stream_read_repair(ofc_stream_t *s, int64_t *counts_host, int max_pairs);
+
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.

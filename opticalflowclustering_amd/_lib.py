@@ -22,6 +22,7 @@ CONSIST_OK, CONSIST_MISMATCH, CONSIST_LEAVES, CONSIST_INVALID, CONSIST_STATES = 
 CONSIST_SHARE, CONSIST_MAX_DIM = 2048, 16384         # OFC_CONSIST_SHARE, OFC_CONSIST_MAX_DIM
 CONSIST_ALPHA_MAX, CONSIST_BETA_MAX = 65536, 1 << 62  # OFC_CONSIST_ALPHA_MAX, OFC_CONSIST_BETA_MAX
 PHOTO_SHARE, PHOTO_TAU_MAX, PHOTO_KAPPA_MAX, PHOTO_NSTAT = 2048, 65280, 1024, 5      # OFC_PHOTO_*
+REPAIR_ROUNDS_MAX, REPAIR_NCOUNT, REPAIR_UNFILLED = 254, 3, 255                      # OFC_REPAIR_*
 
 
 class OfcError(RuntimeError):
@@ -174,6 +175,13 @@ _PROTOS = {
     "ofc_bench_photo": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_stream_set_photo": ([_vp, _i, _i, _i, _i], _i),
     "ofc_stream_read_photo": ([_vp, _vp, _i], _i),
+    "ofc_repair_check": ([_i, _i, _i, _i, _i, _i, _i, _i], _i),
+    "ofc_repair_tile": ([_i, C.POINTER(_i * 2)], None),
+    "ofc_repair_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "ofc_repair": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "ofc_bench_repair": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
+    "ofc_stream_set_repair": ([_vp, _i, _i, _i, _i, _i, _i], _i),
+    "ofc_stream_read_repair": ([_vp, _vp, _i], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

@@ -12,9 +12,12 @@
 // the one from the previous batch's last pair, whose label map, moves and areas the stream carries over.
 // With a photometric check (ofc_stream_set_photo) every pair's vectors are checked against the slot's own frames directly
 // behind the flow, before the camera is subtracted (photo_check.hip); with blobs the key map is masked by the check's states.
+// With a repair (ofc_stream_set_repair) the batch's field is repaired in place directly behind that check, whose state map it
+// takes and updates (flow_repair.hip): before the moves are taken and the camera is fitted, so all of the above see it.
 #include "blob_links.h"
 #include "color_common.h"
 #include "fb_check.h"
+#include "flow_repair.h"
 #include "lloyd_common.h"
 #include "motion_model.h"
 #include "photo_check.h"
@@ -75,6 +78,13 @@ struct ofc_stream {
     DevBuf photo_stats;                // [max_pairs][5] int64: grows with `cells`
     size_t photo_cap = 0;              // pairs
     int photo_pairs = 0;               // pairs of the last finish: what ofc_stream_read_photo delivers
+    // the repair, when there is one (repair_on): every pair's counts, kept past the finish like the photometric stats
+    bool repair_on = false;
+    int repair_keep = 0, repair_radius = 0, repair_rounds = 0, repair_min_count = 0, repair_smooth = 0;
+    DevBuf repair_a, repair_b, repair_filled;   // the snapshots and the filled map of a chunk of a batch (RepairScratch)
+    DevBuf repair_counts;              // [max_pairs][3] int64: grows with `cells`
+    size_t repair_cap = 0;             // pairs
+    int repair_pairs = 0;              // pairs of the last finish: what ofc_stream_read_repair delivers
 };
 
 namespace {
@@ -203,6 +213,24 @@ int ensure_photo(ofc_stream *s, int need_pairs)
     return OFC_OK;
 }
 
+// room for the repair counts of need_pairs pairs: same growth as ensure_photo, what was counted so far is kept
+int ensure_repair(ofc_stream *s, int need_pairs)
+{
+    if ((size_t)need_pairs <= s->repair_cap) return OFC_OK;
+    const size_t cap = std::max<size_t>(need_pairs, s->repair_cap ? s->repair_cap * 2 : 256);
+    const size_t per = sizeof(int64_t) * REPAIR_NCOUNT;
+    DevBuf nb;
+    OFC_TRY(nb.alloc(cap * per));
+    if (s->repair_counts.p && s->pairs_submitted) {
+        OFC_HIP(hipStreamSynchronize(s->compute));
+        OFC_HIP(hipMemcpy(nb.p, s->repair_counts.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
+    }
+    std::swap(s->repair_counts.p, nb.p);
+    std::swap(s->repair_counts.bytes, nb.bytes);
+    s->repair_cap = cap;
+    return OFC_OK;
+}
+
 // Behind a batch's label maps: its areas, then the votes of the transition from the carried pair (when the clip has one
 // before this batch) and of the batch's inner transitions; then the batch's last pair becomes the carried one.
 int submit_links(ofc_stream *s, const int32_t *labels, int npair)
@@ -240,6 +268,7 @@ int submit(ofc_stream *s, int i)
     if (s->blob_conn) OFC_TRY(ensure_blobs(s, s->pairs_submitted + npair));
     if (s->link_max) OFC_TRY(ensure_links(s, s->pairs_submitted + npair));
     if (s->photo_on) OFC_TRY(ensure_photo(s, s->pairs_submitted + npair));
+    if (s->repair_on) OFC_TRY(ensure_repair(s, s->pairs_submitted + npair));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
@@ -249,6 +278,17 @@ int submit(ofc_stream *s, int i)
         OFC_TRY(launch_photo_check(sl.frames.as<uint8_t>(), sl.flows.as<float>(), s->W, s->H, npair, s->photo_tau, s->photo_kappa,
                                    s->photo_state.as<uint8_t>(),
                                    s->photo_stats.as<int64_t>() + (size_t)s->pairs_submitted * PHOTO_NSTAT, nullptr, s->compute));
+    // the repair takes the check's state map (without a check only invalid vectors are targets) and works in place on both:
+    // everything from here on, the moves and the camera included, sees the repaired field and the updated states
+    if (s->repair_on) {
+        RepairScratch rs;
+        rs.a = s->repair_a.as<float>(), rs.b = s->repair_b.as<float>(), rs.filled = s->repair_filled.as<uint8_t>();
+        rs.chunk = repair_chunk_pairs(s->W, s->H, s->batch);
+        uint8_t *st = s->photo_on ? s->photo_state.as<uint8_t>() : nullptr;
+        OFC_TRY(launch_repair(sl.flows.as<float>(), st, s->W, s->H, npair, s->repair_keep, s->repair_radius, s->repair_rounds,
+                              s->repair_min_count, s->repair_smooth != 0, sl.flows.as<float>(), nullptr, st,
+                              s->repair_counts.as<int64_t>() + (size_t)s->pairs_submitted * REPAIR_NCOUNT, rs, s->compute));
+    }
     // where the pixels go is what the whole flow says: the moves are taken before the camera is subtracted
     if (s->link_max) OFC_TRY(launch_blob_moves(sl.flows.as<float>(), s->W, s->H, npair, s->link_moves.as<int32_t>(), s->compute));
     if (s->cam_kind) {
@@ -387,6 +427,7 @@ int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pai
     s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
     s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
     s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
+    s->repair_pairs = s->repair_on ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -438,6 +479,7 @@ int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts,
     s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
     s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
     s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
+    s->repair_pairs = s->repair_on ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
     return OFC_OK;
 }
@@ -668,6 +710,53 @@ int ofc_stream_read_photo(ofc_stream_t *s, int64_t *stats_host, int max_pairs)
     OFC_REQUIRE(stats_host, "null pointer");
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
     OFC_HIP(hipMemcpy(stats_host, s->photo_stats.p, sizeof(int64_t) * PHOTO_NSTAT * (size_t)s->photo_pairs, hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+int ofc_stream_set_repair(ofc_stream_t *s, int on, int keep, int radius, int rounds, int min_count, int smooth)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (on != 0) OFC_TRY(repair_check(s->W, s->H, s->batch, keep, radius, rounds, min_count, smooth));
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: set the repair on a fresh stream or straight after a finish");
+    OFC_TRY(ensure_device(s->device));
+    s->repair_pairs = 0;
+    if (on == 0) {
+        s->repair_a.release();
+        s->repair_b.release();
+        s->repair_filled.release();
+        s->repair_counts.release();
+        s->repair_cap = 0;
+        s->repair_on = false;
+        return OFC_OK;
+    }
+    // a batch's chunk: one snapshot, a second with more than two sweeps, and the filled map the state kernel reads
+    const int chunk = repair_chunk_pairs(s->W, s->H, s->batch);
+    const size_t field = repair_field_bytes(s->W, s->H, chunk), map = repair_filled_bytes(s->W, s->H, chunk);
+    if (s->repair_a.bytes < field) OFC_TRY(s->repair_a.alloc(field));
+    if (rounds + smooth > 2 && s->repair_b.bytes < field) OFC_TRY(s->repair_b.alloc(field));
+    if (s->repair_filled.bytes < map) OFC_TRY(s->repair_filled.alloc(map));
+    s->repair_on = true;
+    s->repair_keep = keep;
+    s->repair_radius = radius;
+    s->repair_rounds = rounds;
+    s->repair_min_count = min_count;
+    s->repair_smooth = smooth;
+    return OFC_OK;
+}
+
+int ofc_stream_read_repair(ofc_stream_t *s, int64_t *counts_host, int max_pairs)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->repair_on, "the stream has no repair (ofc_stream_set_repair)");
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: read the repair counts straight after a finish");
+    OFC_REQUIRE(max_pairs >= s->repair_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->repair_pairs);
+    OFC_TRY(ensure_device(s->device));
+    if (!s->repair_pairs) return OFC_OK;
+    OFC_REQUIRE(counts_host, "null pointer");
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    OFC_HIP(hipMemcpy(counts_host, s->repair_counts.p, sizeof(int64_t) * REPAIR_NCOUNT * (size_t)s->repair_pairs, hipMemcpyDeviceToHost));
     return OFC_OK;
 }
 

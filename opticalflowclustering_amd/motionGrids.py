@@ -47,6 +47,13 @@ contrast (8 and 0.5 by default, a convention that is not tuned here).  It needs 
 route, where it does what --consistent does with its state map, and on --stream and --fit-stream, where the stream's blobs
 keep only the pixels that passed.  --photo-counts writes the (pairs, 5) stats: the pixels per state, then the sum of the
 absolute error in 1/256 grey levels.  The two checks cannot be combined.
+
+With --repair R[:ROUNDS] (any route) the vectors that are not trusted are filled in on the device before anything else looks
+at the field (repair.py): each becomes the median of the trusted vectors in its (2R+1)^2 window, R being 1 or 2, round after
+round, ROUNDS times at the most (8 by default, a convention that is not tuned here).  With --consistent or --photometric the
+vectors that failed the check are the ones filled, and a filled pixel counts as one that passed; without a check only vectors
+that are not usable numbers are.  --repair-smooth adds a median pass over the whole field; --repair-counts writes the
+(pairs, 3) counts: sources, filled, unfilled.
 """
 import argparse
 import os
@@ -186,7 +193,26 @@ def parse_arguments(argv=None):
     ap.add_argument("--photo-kappa", type=float, default=0.5,
                     help="grey levels forgiven per grey level of local contrast (a convention, not tuned)")
     ap.add_argument("--photo-counts", metavar="FILE.npy", help="write the (pairs, 5) stats of the check to this .npy file")
+    ap.add_argument("--repair", metavar="R[:ROUNDS]",
+                    help="fill the vectors that are not trusted by the median of their (2R+1)^2 window, R = 1 or 2, for at most "
+                         "ROUNDS rounds (default 8, a convention, not tuned); any route")
+    ap.add_argument("--repair-smooth", action="store_true", help="a median pass over the whole field behind the fill")
+    ap.add_argument("--repair-counts", metavar="FILE.npy", help="write the (pairs, 3) counts of the repair to this .npy file")
     args = ap.parse_args(argv)
+    args.repair_spec = None
+    if args.repair:
+        try:
+            parts = [int(v) for v in args.repair.split(":")]
+            if len(parts) > 2:
+                raise ValueError
+        except ValueError:
+            ap.error(f"--repair takes R or R:ROUNDS, two integers, got {args.repair!r}")
+        radius, rounds = parts[0], parts[1] if len(parts) == 2 else 8
+        if radius not in (1, 2) or not 0 <= rounds <= 254 or (rounds == 0 and not args.repair_smooth):
+            ap.error("--repair R[:ROUNDS]: R is 1 or 2, ROUNDS 0 .. 254, and 0 only with --repair-smooth")
+        args.repair_spec = dict(radius=radius, rounds=rounds, smooth=args.repair_smooth)
+    elif args.repair_smooth or args.repair_counts:
+        ap.error("--repair-smooth and --repair-counts belong to --repair")
     if args.photometric:
         if args.consistent:
             ap.error("--photometric and --consistent each leave a state map of their own: combining the two is not supported")
@@ -274,6 +300,11 @@ def _save_npy(path, a):
     np.save(path, a)
 
 
+def _print_repair(counts):
+    total = max(int(counts.sum()), 1)
+    print("repair: " + ", ".join(f"{100.0 * c / total:.2f} % {name}" for name, c in zip(("sources", "filled", "unfilled"), counts.sum(0))))
+
+
 def _print_photometric(stats, tau_q, kappa_q):
     from .photometric import STATE_NAMES, Photometric
     ph = Photometric(None, stats, None, tau_q, kappa_q)
@@ -283,10 +314,11 @@ def _print_photometric(stats, tau_q, kappa_q):
 
 
 def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None, blobs=None, blobs_out=None,
-                  max_links=0, photometric=None, photo_out=None):
+                  max_links=0, photometric=None, photo_out=None, repair=None, repair_out=None):
     """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident; camera as
     FlowStream's, its (pairs, 6) models saved to camera_out; blobs as FlowStream's, their rows written to blobs_out, with
-    max_links linked and with their track ids; photometric as FlowStream's, its (pairs, 5) stats saved to photo_out"""
+    max_links linked and with their track ids; photometric as FlowStream's, its (pairs, 5) stats saved to photo_out; repair
+    as FlowStream's, its (pairs, 3) counts saved to repair_out"""
     from .stream import FlowStream
     fs, n = None, 0
     if blobs is not None and max_links:
@@ -295,7 +327,7 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
         for gray in gray_frames(path, device):
             if fs is None:
                 fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, centers=centers,
-                                camera=camera, blobs=blobs, photometric=photometric)
+                                camera=camera, blobs=blobs, photometric=photometric, repair=repair)
             fs.push(gray)
             n += 1
         if n < 2:
@@ -310,21 +342,27 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
             _print_photometric(stats, *fs.photo_args[:2])
             if photo_out:
                 _save_npy(photo_out, stats)
+        if repair is not None:
+            filled = fs.repair_stats()
+            _print_repair(filled)
+            if repair_out:
+                _save_npy(repair_out, filled)
         return counts
     finally:
         if fs is not None:
             fs.close()
 
 
-def stream_histogram(path, bins, range, rows=14, cols=25, batch_pairs=8, device=0, camera=None):
-    """the (u,v) histogram (uvhist.UVHistogram) of a clip that is read frame by frame and never resident"""
+def stream_histogram(path, bins, range, rows=14, cols=25, batch_pairs=8, device=0, camera=None, photometric=None, repair=None):
+    """the (u,v) histogram (uvhist.UVHistogram) of a clip that is read frame by frame and never resident; with repair (and the
+    photometric check that says what to repair) as FlowStream's, of the repaired field"""
     from .stream import FlowStream
     fs, n = None, 0
     try:
         for gray in gray_frames(path, device):
             if fs is None:
                 fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, histogram=(bins, range),
-                                camera=camera)
+                                camera=camera, photometric=photometric if repair is not None else None, repair=repair)
             fs.push(gray)
             n += 1
         if n < 2:
@@ -343,19 +381,21 @@ def main(argv=None):
         _load_centres(args.init, k, "--init") if args.init != "k-means++" else None
     if args.fit_stream:
         hist = stream_histogram(args.path, args.hist_bins, args.hist_range, args.rows, args.cols, args.batch_pairs, args.device,
-                                args.camera_spec)
+                                args.camera_spec, args.photo_spec, args.repair_spec)
         total = hist.n + hist.outside
         print(f"histogram: {hist.n} vectors in {int(np.count_nonzero(hist.counts))} bins, {hist.outside} outside "
               f"[-{args.hist_range:g}, {args.hist_range:g}) px ({100.0 * hist.outside / max(total, 1):.4f} %)")
         centers, _, _ = hist.fit(k, init="k-means++" if given is None else given, random_state=args.seed, n_init=args.n_init,
                                  device=args.device)
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts)
+                               args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts,
+                               args.repair_spec, args.repair_counts)
         return _write_outputs(args, counts, centers)
     if args.stream:
         centers = given
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
-                               args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts)
+                               args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts,
+                               args.repair_spec, args.repair_counts)
         return _write_outputs(args, counts, centers)
     from .pipeline import ClipPipeline
     frames = read_gray_frames(args.path, args.device)
@@ -380,6 +420,11 @@ def main(argv=None):
             if args.photo_counts:
                 _save_npy(args.photo_counts, checked.stats)
             fb = True
+        if args.repair_spec:                    # a repaired vector says where a pixel lands: before the camera is taken out
+            filled = pipe.repair(need_state=False, **args.repair_spec)
+            _print_repair(filled)
+            if args.repair_counts:
+                _save_npy(args.repair_counts, filled)
         if args.camera_spec:
             if args.max_links:
                 pipe.capture_moves()            # where the pixels go: before the camera is taken out of the field

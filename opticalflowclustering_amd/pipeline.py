@@ -61,6 +61,7 @@ class ClipPipeline:
         self.frames_rev = None              # run_backward_flow(): the resident frames in reverse order, n_frames * P u8
         self.flows_bwd = None               # ... and the field of that clip: pair t's backward field at n_pairs-1-t
         self.state = None                   # consistency() / photometric(): the state map of the check that ran last, n_pairs * P u8
+        self.filled = None                  # repair(): the round every pixel was filled in, n_pairs * P u8
 
     def synth(self, t0=0, seed=0):
         """fill the resident clip with synthetic frames t0 .. t0+n_frames-1"""
@@ -91,7 +92,7 @@ class ClipPipeline:
             self.sync()
 
     def _drop_backward(self):
-        for name in ("frames_rev", "flows_bwd", "state"):
+        for name in ("frames_rev", "flows_bwd", "state", "filled"):
             b = getattr(self, name)
             if b is not None:
                 b.free()
@@ -185,6 +186,47 @@ class ClipPipeline:
             raise
         return photo.Photometric(self.state.download((n, H, W), np.uint8), np.concatenate(stats),
                                  np.concatenate(out) if warped else None, tau_q, kappa_q)
+
+    def repair(self, radius=1, rounds=8, min_count=1, smooth=False, keep=(0,), need_state=True):
+        """the masked median fill of the resident field, in place (repair.py; ofc_repair_dev), in chunks of at most 65535
+        pairs -> (n,3) int64, every pair's sources, filled and unfilled pixels.  The sources are the pixels whose state in
+        the map that consistency() or photometric() left is in `keep` (consistency.keep_mask); ValueError when there is no
+        such map (need_state=False: then only the vectors that are not usable numbers are filled).  Every other pixel is replaced by the median of the sources around it, round after round; smooth adds a
+        median pass over the whole field.  The state map is updated: a filled pixel becomes CONSISTENT, so
+        blobs(consistent=True) and run_kmeans / seed_kmeans(consistent=True) take it back in.  The round every pixel was
+        filled in stays on the device: filled_host().  rounds and min_count default to 8 and 1, a convention, not tuned
+        on anything here.  ValueError after compensate_camera(): a repaired vector says where a pixel lands, so
+        repair before the camera is removed.  The batch sums of the flow no longer describe the field afterwards, so
+        run_kmeans sweeps it for its column means.  Rank-local: a pair depends on itself alone."""
+        from . import repair as rep
+        kp = rep.keep_mask(keep)
+        if self.state is None and need_state:
+            raise ValueError("repair() needs the state map of a check: call photometric(), or run_backward_flow() and "
+                             "consistency(), first (run_flow() discards them)")
+        if self._compensated:
+            raise ValueError("repair() after compensate_camera() would fill the residual, which does not say where a pixel "
+                             "lands: call it before compensate_camera()")
+        self.sync()
+        n, W, H = self.n_pairs, self.W, self.H
+        P = W * H
+        rep.check_args(W, H, min(n, 65535), kp, radius, rounds, min_count, smooth)
+        if self.filled is None:
+            self.filled = DeviceBuffer(n * P, self.device)
+        counts = []
+        for t0 in range(0, n, 65535):
+            m = min(65535, n - t0)
+            st = self.state.ptr + t0 * P if self.state is not None else None
+            counts.append(rep.fill_dev(self.flows.ptr + t0 * P * 8, st, W, H, m, None, self.filled.ptr + t0 * P, st, kp, radius,
+                                       rounds, min_count, smooth, self.device))
+        self._sums_valid = False
+        self._label_k = None                # the labels belong to the field as it was
+        return np.concatenate(counts)
+
+    def filled_host(self):
+        """host copy of repair()'s map: (n,H,W) u8, 0 for a source, g for a pixel filled in round g, 255 for one never filled"""
+        if self.filled is None:
+            raise ValueError("no filled map: call repair() first (run_flow() discards it)")
+        return self.filled.download((self.n_pairs, self.H, self.W), np.uint8)
 
     def _state_ptr(self, what):
         if self.state is None:

@@ -10,7 +10,9 @@ on the device straight after the flow (camera.py), and all of the above see the 
 (blobs=dict(thr=...)) every pair's moving regions are labelled and described on the device as well (blobs.py): blobs();
 with max_links among them the blobs of consecutive pairs are linked too, inside a batch and across batches (blobs.tracks).
 With a photometric check (photometric=True or dict(tau=, kappa=, keep=)) every pair's vectors are checked against the batch's
-own frames (photometric.py): photometric_stats(), and the blobs keep only the pixels that passed."""
+own frames (photometric.py): photometric_stats(), and the blobs keep only the pixels that passed.
+With a repair (repair=True or dict(radius=, rounds=, min_count=, smooth=, keep=)) the vectors that check flagged are filled
+in by the median of their trusted neighbours before anything else looks at the field (repair.py): repair_stats()."""
 import ctypes as C
 
 import numpy as np
@@ -20,7 +22,7 @@ from ._lib import FbParams, check, load, ptr
 
 class FlowStream:
     def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False,
-                 histogram=None, camera=None, blobs=None, photometric=None):
+                 histogram=None, camera=None, blobs=None, photometric=None, repair=None):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
@@ -44,6 +46,36 @@ class FlowStream:
         self.photo_args = None              # (tau_q, kappa_q, keep) of the stream's photometric check, or None
         if photometric is not None and photometric is not False:
             self.set_photometric(**({} if photometric is True else photometric))
+        self.repair_args = None             # (keep, radius, rounds, min_count, smooth) of the stream's repair, or None
+        if repair is not None and repair is not False:
+            self.set_repair(**({} if repair is True else repair))
+
+    def set_repair(self, radius=1, rounds=8, min_count=1, smooth=False, keep=(0,), on=True):
+        """from the next batch on, repair every batch's field in place (ofc_stream_set_repair; repair.py has the definition)
+        directly behind the photometric check, whose states say which vectors are sources (those in `keep`,
+        consistency.keep_mask) and are updated: a filled pixel counts as CONSISTENT, so on a stream with blobs it belongs to
+        them again.  Without a photometric check only vectors that are not usable numbers are filled.  It runs before the
+        links' moves are taken and before a camera is fitted, so the cell means, the model's counts, the histogram, the
+        camera and the blobs all see the repaired field.  on=False removes it.  rounds and min_count default to 8 and 1, a
+        convention that is not tuned on anything here.  Only on a stream that holds no frame and no undelivered result, as
+        set_model; ValueError otherwise, and nothing changes."""
+        if not on:
+            check(load().ofc_stream_set_repair(self._h, 0, 0, 0, 0, 0, 0))
+            self.repair_args, self._last_pairs = None, 0
+            return
+        from .consistency import keep_mask
+        args = (keep_mask(keep), int(radius), int(rounds), int(min_count), int(bool(smooth)))
+        check(load().ofc_stream_set_repair(self._h, 1, *args))
+        self.repair_args, self._last_pairs = args, 0
+
+    def repair_stats(self):
+        """-> (n, 3) int64 of the pairs the last finish() / finish_clusters() delivered (ofc_stream_read_repair): every pair's
+        sources, filled and unfilled pixels.  Straight after a finish only; ValueError once frames are held again, and on a
+        stream without the repair."""
+        n = self._last_pairs
+        counts = np.zeros((max(n, 1), 3), np.int64)
+        check(load().ofc_stream_read_repair(self._h, ptr(counts), max(n, 1)))
+        return counts[:n]
 
     def set_photometric(self, tau=8.0, kappa=0.5, keep=(0,), on=True):
         """from the next batch on, put every pair's vectors to the photometric check against the batch's own frames
