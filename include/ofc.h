@@ -108,6 +108,15 @@ int ofc_flow_calc_frames_dev(ofc_flow_t *f, const uint8_t *frames_dev, int n_fra
 int ofc_flow_calc_frames_dev_stats(ofc_flow_t *f, const uint8_t *frames_dev, int n_frames,
                                    float *flow_dev, double *uv_sum_dev);
 int ofc_flow_sync(ofc_flow_t *f);
+/* *on = 1 when the engine runs the front end of the coarse pyramid levels (level images and polynomial expansions, which
+ * depend on the frames only) on a side stream beside the level-0 expansion, 0 when it runs every level in series on one
+ * stream.  Either order launches the same kernels with the same arguments: the results are the same bits.  The overlap
+ * gives every level its own slices of the I and R scratch, so an engine uses it only when those slices together are at most
+ * 1.5 x the level-0 sized buffers of the serial order (pyr_scale 0.5: up to 1.33 x; a deep pyramid at pyr_scale 0.8 stays
+ * serial), when the pyramid has a coarse level at all, and when neither OFC_FLOW_FRONT_OVERLAP=0 nor OFC_FLOW_GRAPH=1 was
+ * set in the environment when the engine was created.  Everything a call issues is ordered before whatever follows it on
+ * the engine's stream: callers synchronise as before. */
+int ofc_flow_front_overlap(const ofc_flow_t *f, int *on);
 
 /* streaming form of ComputeOpticalFLow (computeOpticalFlowModule.py:6-36): keeps the previous
  * frame; the first push returns OFC_ENOTREADY and writes nothing.

@@ -64,6 +64,7 @@ _PROTOS = {
     "ofc_flow_calc_frames_dev": ([_vp, _vp, _i, _vp], _i),
     "ofc_flow_calc_frames_dev_stats": ([_vp, _vp, _i, _vp, _vp], _i),
     "ofc_flow_sync": ([_vp], _i),
+    "ofc_flow_front_overlap": ([_vp, _ip], _i),
     "ofc_flow_push_gray": ([_vp, _vp, _vp], _i),
     "ofc_flow_push_bgr": ([_vp, _vp, _vp, C.POINTER(_f), _vp], _i),
     "ofc_flow_last_vis_dev": ([_vp, C.POINTER(_vp)], _i),

@@ -224,6 +224,16 @@ struct ofc_flow {
     std::vector<LevelGeom> geom;    // [0..levels]
     hipStream_t stream = nullptr;
     DevBuf I, R, M, flowA, flowB, flowC;   // scratch sized for level 0 and max_batch
+    // Front end beside the level-0 expansion: the level images and expansions of levels 1.. depend on
+    // the frames only and are latency-bound chains of many short work-groups that fit beside the level-0 expansion's, so
+    // they run on `side` while `stream` runs the level-0 front end, and every level's iterations wait for that level's
+    // `ready` event.  Each level then needs its own slice of I and R (offI / offR, in floats; all zero in the serial order,
+    // where every level reuses the level-0 sized buffers).  OFC_FLOW_FRONT_OVERLAP=0 forces the serial order (ofc_flow_create).
+    bool front_overlap = false;
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr;
+    std::vector<hipEvent_t> ready;  // [0..levels], [0] unused (null)
+    std::vector<size_t> offI, offR; // [0..levels]
     bool fused = true;              // update-matrices fused into the box/solve kernel (winsize <= 15); otherwise the staged
                                     // kernels: k_box_solve<8> at 17, k_box_solve_wide from 19 on
     bool fuse_level0 = true;        // polyexp of level 0 reads the u8 frames (no f32 level-0 image)
@@ -263,10 +273,29 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
     const int npair = n_frames - 1;
     const int W = f->W, H = f->H;
     hipStream_t s = f->stream;
-    float *I = f->I.as<float>(), *R = f->R.as<float>();
     const int iters = f->prm.iterations;
     float *prevFlow = nullptr;
     int pw = 0, ph = 0;
+    // a level's front end: level image and polynomial expansion of the batch's frames into the level's slices of I and R
+    auto front_end = [&](int k, hipStream_t st) -> int {
+        float *I = f->I.as<float>() + f->offI[k], *R = f->R.as<float>() + f->offR[k];
+        const LevelGeom &g = f->geom[k];
+        if (k == 0 && f->fuse_level0 && polyexp_u8_ok(W, H, g)) return launch_polyexp_u8(frames_dev, R, n_frames, W, H, f->pc, st);
+        OFC_TRY(launch_level_image(frames_dev, I, n_frames, W, H, g, st));
+        return launch_polyexp(I, R, n_frames, g.w, g.h, f->pc, 0, st);
+    };
+    if (f->front_overlap) {
+        // fork behind everything the main stream holds: the copies of the frames, and the previous call's iterations, which
+        // still read the per-level R.  Then the coarse levels' front ends on the side stream, coarsest first (the order the
+        // iterations want them in), and the level-0 front end beside them on the main stream.
+        OFC_HIP(hipEventRecord(f->fork, s));
+        OFC_HIP(hipStreamWaitEvent(f->side, f->fork, 0));
+        for (int k = f->levels; k >= 1; k--) {
+            OFC_TRY(front_end(k, f->side));
+            OFC_HIP(hipEventRecord(f->ready[k], f->side));
+        }
+        OFC_TRY(front_end(0, s));
+    }
     for (int k = f->levels; k >= 0; k--) {
         const LevelGeom &g = f->geom[k];
         const size_t P = (size_t)g.w * g.h;
@@ -274,11 +303,12 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
         // dst and tmp, so the initial flow goes to whichever makes the last iteration write dst
         float *dst = (k == 0) ? flow_dev : (((f->levels - k) & 1) ? f->flowB.as<float>() : f->flowA.as<float>());
         float *tmp = f->flowC.as<float>();
-        if (k == 0 && f->fuse_level0 && polyexp_u8_ok(W, H, g)) {
-            OFC_TRY(launch_polyexp_u8(frames_dev, R, n_frames, W, H, f->pc, s));
-        } else {
-            OFC_TRY(launch_level_image(frames_dev, I, n_frames, W, H, g, s));
-            OFC_TRY(launch_polyexp(I, R, n_frames, g.w, g.h, f->pc, 0, s));
+        const float *R = f->R.as<float>() + f->offR[k];
+        if (!f->front_overlap) {
+            OFC_TRY(front_end(k, s));
+        } else if (k >= 1) {
+            // after the wait at level 1 the side stream is joined: whatever a caller could wait for is reachable from `s`
+            OFC_HIP(hipStreamWaitEvent(s, f->ready[k], 0));
         }
         const size_t strideR = 5 * P;
         const float mul = (float)(1. / f->prm.pyr_scale);
@@ -414,7 +444,7 @@ int ofc_flow_create(int device, int W, int H, const ofc_fb_params *p, int max_ba
     OFC_TRY(check_params(prm, W, H));
     OFC_REQUIRE(max_batch >= 1 && max_batch <= 4096, "max_batch out of range");
     OFC_REQUIRE((prm.winsize & 1) && prm.winsize >= 5, "winsize must be odd and >= 5");
-    std::unique_ptr<ofc_flow> f(new ofc_flow);
+    std::unique_ptr<ofc_flow, void (*)(ofc_flow_t *)> f(new ofc_flow, ofc_flow_destroy);   // a failure below leaves no stream or event behind
     f->device = device; f->W = W; f->H = H; f->max_batch = max_batch; f->prm = prm;
     f->levels = pyramid_levels(W, H, prm);
     for (int k = 0; k <= f->levels; k++) f->geom.push_back(level_geometry(W, H, prm, k));
@@ -445,8 +475,41 @@ int ofc_flow_create(int device, int W, int H, const ofc_fb_params *p, int max_ba
     polyexp_setup(prm.poly_n, prm.poly_sigma, f->pc);
     OFC_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
     const size_t P0 = (size_t)W * H, nb = (size_t)max_batch;
-    OFC_TRY(f->I.alloc(sizeof(float) * P0 * (nb + 1)));
-    OFC_TRY(f->R.alloc(sizeof(float) * 5 * P0 * (nb + 1)));
+    size_t nI = P0 * (nb + 1), nR = 5 * P0 * (nb + 1);          // floats: one level-0 sized buffer each, shared by the levels
+    f->offI.assign(f->levels + 1, 0);
+    f->offR.assign(f->levels + 1, 0);
+    {
+        // a slice of R per level, and of I per level that has a level image (level 0 has none when its expansion reads the
+        // u8 frames), each 256-byte aligned as an allocation of its own would be
+        const bool u8_level0 = f->fuse_level0 && polyexp_u8_ok(W, H, f->geom[0]);
+        std::vector<size_t> oI(f->levels + 1, 0), oR(f->levels + 1, 0);
+        size_t sI = 0, sR = 0;
+        for (int k = 0; k <= f->levels; k++) {
+            const size_t Pk = (size_t)f->geom[k].w * f->geom[k].h;
+            oR[k] = sR;
+            sR += (5 * Pk * (nb + 1) + 63) & ~(size_t)63;
+            oI[k] = sI;
+            if (k > 0 || !u8_level0) sI += (Pk * (nb + 1) + 63) & ~(size_t)63;
+        }
+        // On unless OFC_FLOW_FRONT_OVERLAP=0 forces the serial order (A/B runs, the parity test), when there is a coarse
+        // level to run aside, the order is not captured into a graph (a capture must stay one chain), and the slices
+        // together stay within 1.5 x the shared buffers: a deep pyramid at a pyr_scale near 1 must not multiply the
+        // engine's memory.
+        const char *eo = getenv("OFC_FLOW_FRONT_OVERLAP");
+        f->front_overlap = !(eo && eo[0] == '0') && f->levels >= 1 && !f->use_graph && 2 * (sI + sR) <= 3 * (nI + nR);
+        if (f->front_overlap) {
+            f->offI = oI; f->offR = oR;
+            nI = sI; nR = sR;
+        }
+    }
+    if (f->front_overlap) {
+        OFC_HIP(hipStreamCreateWithFlags(&f->side, hipStreamNonBlocking));
+        OFC_HIP(hipEventCreateWithFlags(&f->fork, hipEventDisableTiming));
+        f->ready.assign(f->levels + 1, nullptr);
+        for (int k = 1; k <= f->levels; k++) OFC_HIP(hipEventCreateWithFlags(&f->ready[k], hipEventDisableTiming));
+    }
+    OFC_TRY(f->I.alloc(sizeof(float) * nI));
+    OFC_TRY(f->R.alloc(sizeof(float) * nR));
     if (f->fused) {
         OFC_TRY(f->flowC.alloc(sizeof(float) * 2 * P0 * nb));
     } else {
@@ -465,11 +528,15 @@ int ofc_flow_create(int device, int W, int H, const ofc_fb_params *p, int max_ba
 void ofc_flow_destroy(ofc_flow_t *f)
 {
     if (!f) return;
-    (void)hipSetDevice(f->device);
-    if (f->stream) {
-        (void)hipStreamSynchronize(f->stream);
-        (void)hipStreamDestroy(f->stream);
-    }
+    if (f->stream) (void)hipSetDevice(f->device);   // (an engine refused before it touched the device has nothing there)
+    // both streams drain and go before any buffer is freed: the side stream may still write the coarse levels' I and R
+    for (hipStream_t s : {f->stream, f->side})
+        if (s) (void)hipStreamSynchronize(s);
+    for (hipStream_t s : {f->stream, f->side})
+        if (s) (void)hipStreamDestroy(s);
+    if (f->fork) (void)hipEventDestroy(f->fork);
+    for (hipEvent_t e : f->ready)
+        if (e) (void)hipEventDestroy(e);
     for (auto &g : f->graphs) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
         if (g.graph) (void)hipGraphDestroy(g.graph);
@@ -502,6 +569,13 @@ int ofc_flow_sync(ofc_flow_t *f)
     OFC_REQUIRE(f, "null pointer");
     OFC_TRY(ensure_device(f->device));
     OFC_HIP(hipStreamSynchronize(f->stream));
+    return OFC_OK;
+}
+
+int ofc_flow_front_overlap(const ofc_flow_t *f, int *on)
+{
+    OFC_REQUIRE(f && on, "null pointer");
+    *on = f->front_overlap ? 1 : 0;
     return OFC_OK;
 }
 

@@ -61,6 +61,14 @@ class FlowEngine:
     def sync(self):
         check(load().ofc_flow_sync(self._h))
 
+    def front_overlap(self):
+        """True when the engine runs the coarse levels' front end on a side stream beside the level-0 expansion, False when
+        it runs the levels in series (OFC_FLOW_FRONT_OVERLAP=0 or OFC_FLOW_GRAPH=1 at creation, no coarse level, or per-level
+        scratch beyond 1.5 x the shared buffers); the results are the same bits either way"""
+        on = C.c_int(-1)
+        check(load().ofc_flow_front_overlap(self._h, C.byref(on)))
+        return bool(on.value)
+
     def close(self):
         if getattr(self, "_h", None):
             load().ofc_flow_destroy(self._h)
