@@ -1,6 +1,7 @@
 // blob_links_api.cpp -- C ABI of libofc.so, part 8: the links between the blobs of consecutive pairs (blob_links.hip) on
 // device and host buffers, the host forms of its check and of its table's size, and its measurement hook.
 #include "blob_links.h"
+#include "host_util.h"
 
 #include <mutex>
 
@@ -14,17 +15,7 @@ struct LinkScratch {
     std::mutex mu;
 };
 
-LinkScratch &scratch_for(int device)
-{
-    static LinkScratch *pool = new LinkScratch[16];        // intentionally never destroyed (no HIP calls at exit)
-    return pool[device & 15];
-}
-
-int ensure(DevBuf &b, size_t need)
-{
-    if (b.bytes >= need) return OFC_OK;
-    return b.alloc(need);
-}
+LinkScratch &scratch_for(int device) { return device_scratch<LinkScratch>(device); }
 
 // where the votes begin in a links_dev of ntrans transitions (blob_links_bytes' layout)
 int32_t *votes_of(const void *links, int max_links, int ntrans)
@@ -40,7 +31,7 @@ int links_dev(LinkScratch &sc, const int32_t *labels, const int32_t *moves, int 
     const size_t P = (size_t)W * H;
     uint64_t *keys = static_cast<uint64_t *>(links);
     int32_t *votes = votes_of(links, max_links, npair - 1);
-    OFC_TRY(ensure(sc.areas, sizeof(int32_t) * P * npair));
+    OFC_TRY(reserve(sc.areas, sizeof(int32_t) * P * npair));
     int32_t *areas = sc.areas.as<int32_t>();
     OFC_TRY(launch_blob_area(labels, W, H, npair, areas, s));
     OFC_TRY(launch_blob_links_clear(max_links, npair - 1, keys, votes, counters, s));
@@ -143,11 +134,11 @@ int ofc_blob_links(int device, const int32_t *labels_host, const float *flow_hos
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t n = (size_t)W * H * npair;
     const int ntrans = npair - 1;
-    OFC_TRY(ensure(sc.labels, sizeof(int32_t) * n));
-    OFC_TRY(ensure(sc.flow, sizeof(float) * 2 * n));
-    OFC_TRY(ensure(sc.moves, sizeof(int32_t) * n));
-    OFC_TRY(ensure(sc.links, std::max<size_t>(blob_links_bytes(max_links, ntrans), 8)));
-    OFC_TRY(ensure(sc.counters, sizeof(int32_t) * std::max(ntrans, 1)));
+    OFC_TRY(reserve(sc.labels, sizeof(int32_t) * n));
+    OFC_TRY(reserve(sc.flow, sizeof(float) * 2 * n));
+    OFC_TRY(reserve(sc.moves, sizeof(int32_t) * n));
+    OFC_TRY(reserve(sc.links, std::max<size_t>(blob_links_bytes(max_links, ntrans), 8)));
+    OFC_TRY(reserve(sc.counters, sizeof(int32_t) * std::max(ntrans, 1)));
     OFC_HIP(hipMemcpy(sc.labels.p, labels_host, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     OFC_HIP(hipMemcpy(sc.flow.p, flow_host, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
     OFC_TRY(launch_blob_moves(sc.flow.as<float>(), W, H, npair, sc.moves.as<int32_t>(), nullptr));
@@ -171,14 +162,13 @@ int ofc_bench_blob_links(int device, const int32_t *labels_dev, const float *flo
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t P = (size_t)W * H, n = P * npair;
     const int ntrans = npair - 1;
-    OFC_TRY(ensure(sc.moves, sizeof(int32_t) * n));
-    OFC_TRY(ensure(sc.areas, sizeof(int32_t) * n));
-    OFC_TRY(ensure(sc.links, std::max<size_t>(blob_links_bytes(MAXL, ntrans), 8)));
-    OFC_TRY(ensure(sc.counters, sizeof(int32_t) * std::max(ntrans, 1)));
+    OFC_TRY(reserve(sc.moves, sizeof(int32_t) * n));
+    OFC_TRY(reserve(sc.areas, sizeof(int32_t) * n));
+    OFC_TRY(reserve(sc.links, std::max<size_t>(blob_links_bytes(MAXL, ntrans), 8)));
+    OFC_TRY(reserve(sc.counters, sizeof(int32_t) * std::max(ntrans, 1)));
     hipStream_t s = nullptr;
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
+    EventPair ev;
+    OFC_TRY(ev.create());
     int32_t *moves = sc.moves.as<int32_t>(), *areas = sc.areas.as<int32_t>(), *counters = sc.counters.as<int32_t>();
     uint64_t *keys = sc.links.as<uint64_t>();
     int32_t *votes = votes_of(sc.links.p, MAXL, ntrans);
@@ -186,7 +176,7 @@ int ofc_bench_blob_links(int device, const int32_t *labels_dev, const float *flo
     // one run of the chain, the chosen part between the two events
     auto run = [&](bool timed) -> int {
         auto mark = [&](bool begin, bool here) -> int {
-            if (timed && here) OFC_HIP(hipEventRecord(begin ? e0 : e1, s));
+            if (timed && here) OFC_HIP(hipEventRecord(begin ? ev.e0 : ev.e1, s));
             return OFC_OK;
         };
         OFC_TRY(mark(true, what == 0 || what == 3));
@@ -199,19 +189,12 @@ int ofc_bench_blob_links(int device, const int32_t *labels_dev, const float *flo
         OFC_TRY(launch_blob_links_clear(MAXL, ntrans, keys, votes, counters, s));
         OFC_TRY(launch_blob_links(labels_dev, moves, areas, labels_dev + P, areas + P, W, H, ntrans, 1, MAXL, keys, votes, counters, s));
         OFC_TRY(mark(false, what == 2 || what == 3));
-        if (timed) {
-            OFC_HIP(hipEventSynchronize(e1));
-            float ms = 0;
-            OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-            total += ms;
-        }
+        if (timed) OFC_TRY(ev.add_elapsed(total));
         return OFC_OK;
     };
     for (int w = 0; w < 2; w++) OFC_TRY(run(false));
     for (int i = 0; i < iters; i++) OFC_TRY(run(true));
     OFC_HIP(hipStreamSynchronize(s));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *ms_per_run = (float)(total / iters);
     return OFC_OK;
 }

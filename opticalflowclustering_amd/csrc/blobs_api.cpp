@@ -1,6 +1,7 @@
 // blobs_api.cpp -- C ABI of libofc.so, part 7: connected components of a key map (blobs.hip) on device and host buffers,
 // the host forms of its checks and of the table's order, and its measurement hook.
 #include "blobs.h"
+#include "host_util.h"
 
 #include <mutex>
 
@@ -16,17 +17,7 @@ struct BlobScratch {
     std::mutex mu;
 };
 
-BlobScratch &scratch_for(int device)
-{
-    static BlobScratch *pool = new BlobScratch[16];        // intentionally never destroyed (no HIP calls at exit)
-    return pool[device & 15];
-}
-
-int ensure(DevBuf &b, size_t need)
-{
-    if (b.bytes >= need) return OFC_OK;
-    return b.alloc(need);
-}
+BlobScratch &scratch_for(int device) { return device_scratch<BlobScratch>(device); }
 
 int check_keys_args(int use_thr, float thr, int k, const double *mean, const double *centers_c)
 {
@@ -38,7 +29,7 @@ int check_keys_args(int use_thr, float thr, int k, const double *mean, const dou
 // the key kernel's model on the device: mean, centred centres, |c|^2
 int set_model(BlobScratch &sc, int k, const double *mean, const double *centers_c, hipStream_t s)
 {
-    OFC_TRY(ensure(sc.state, sizeof(LloydState)));
+    OFC_TRY(reserve(sc.state, sizeof(LloydState)));
     LloydState st;
     memset(&st, 0, sizeof(st));
     if (mean) memcpy(st.mean, mean, sizeof(double) * 2);
@@ -58,7 +49,7 @@ int keys_dev(BlobScratch &sc, const float *flow_dev, int W, int H, int npair, in
 // the three stages, then the error word: OFC_EHIP when a capped loop ran out
 int label_dev(BlobScratch &sc, const uint8_t *keys, int W, int H, int npair, int connectivity, int32_t *labels, hipStream_t s)
 {
-    OFC_TRY(ensure(sc.err, sizeof(int)));
+    OFC_TRY(reserve(sc.err, sizeof(int)));
     int *err = sc.err.as<int>();
     OFC_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
     OFC_TRY(launch_blob_local(keys, W, H, npair, connectivity, labels, err, s));
@@ -77,7 +68,7 @@ int label_dev(BlobScratch &sc, const uint8_t *keys, int W, int H, int npair, int
 int table_dev(BlobScratch &sc, const uint8_t *keys, const int32_t *labels, const float *flow, int W, int H, int npair,
               int min_area, int max_blobs, int64_t *table, int32_t *found, hipStream_t s)
 {
-    OFC_TRY(ensure(sc.words, sizeof(int32_t) * (size_t)W * H * npair));
+    OFC_TRY(reserve(sc.words, sizeof(int32_t) * (size_t)W * H * npair));
     return launch_blob_table(keys, labels, flow, W, H, npair, min_area, max_blobs, sc.words.as<int32_t>(), table, found, s);
 }
 
@@ -174,12 +165,12 @@ int ofc_blobs(int device, const uint8_t *keys_host, const float *flow_host, int 
     BlobScratch &sc = scratch_for(device);
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t n = (size_t)W * H * npair;
-    OFC_TRY(ensure(sc.keys, n));
-    OFC_TRY(ensure(sc.labels, sizeof(int32_t) * n));
-    OFC_TRY(ensure(sc.table, sizeof(int64_t) * BLOB_NF * (size_t)max_blobs * npair));
-    OFC_TRY(ensure(sc.found, sizeof(int32_t) * npair));
+    OFC_TRY(reserve(sc.keys, n));
+    OFC_TRY(reserve(sc.labels, sizeof(int32_t) * n));
+    OFC_TRY(reserve(sc.table, sizeof(int64_t) * BLOB_NF * (size_t)max_blobs * npair));
+    OFC_TRY(reserve(sc.found, sizeof(int32_t) * npair));
     if (flow_host) {
-        OFC_TRY(ensure(sc.flow, sizeof(float) * 2 * n));
+        OFC_TRY(reserve(sc.flow, sizeof(float) * 2 * n));
         OFC_HIP(hipMemcpy(sc.flow.p, flow_host, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
     }
     const float *flow = flow_host ? sc.flow.as<float>() : nullptr;
@@ -207,24 +198,23 @@ int ofc_bench_blobs(int device, const uint8_t *keys_dev_, const float *flow_dev,
     BlobScratch &sc = scratch_for(device);
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t n = (size_t)W * H * npair;
-    OFC_TRY(ensure(sc.keys, n));
-    OFC_TRY(ensure(sc.labels, sizeof(int32_t) * n));
-    OFC_TRY(ensure(sc.words, sizeof(int32_t) * n));
-    OFC_TRY(ensure(sc.table, sizeof(int64_t) * BLOB_NF * (size_t)MAXB * npair));
-    OFC_TRY(ensure(sc.found, sizeof(int32_t) * npair));
-    OFC_TRY(ensure(sc.err, sizeof(int)));
+    OFC_TRY(reserve(sc.keys, n));
+    OFC_TRY(reserve(sc.labels, sizeof(int32_t) * n));
+    OFC_TRY(reserve(sc.words, sizeof(int32_t) * n));
+    OFC_TRY(reserve(sc.table, sizeof(int64_t) * BLOB_NF * (size_t)MAXB * npair));
+    OFC_TRY(reserve(sc.found, sizeof(int32_t) * npair));
+    OFC_TRY(reserve(sc.err, sizeof(int)));
     OFC_HIP(hipMemset(sc.err.p, 0, sizeof(int)));
     hipStream_t s = nullptr;
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
+    EventPair ev;
+    OFC_TRY(ev.create());
     int32_t *labels = sc.labels.as<int32_t>();
     int *err = sc.err.as<int>();
     double total = 0;
     // one run of the chain, the chosen part between the two events
     auto run = [&](bool timed) -> int {
         auto mark = [&](bool begin, int first, int last) -> int {
-            if (timed && (begin ? first : last)) OFC_HIP(hipEventRecord(begin ? e0 : e1, s));
+            if (timed && (begin ? first : last)) OFC_HIP(hipEventRecord(begin ? ev.e0 : ev.e1, s));
             return OFC_OK;
         };
         OFC_TRY(mark(true, what == 0, 0));
@@ -243,19 +233,12 @@ int ofc_bench_blobs(int device, const uint8_t *keys_dev_, const float *flow_dev,
         OFC_TRY(launch_blob_table(keys_dev_, labels, flow_dev, W, H, npair, 1, MAXB, sc.words.as<int32_t>(), sc.table.as<int64_t>(),
                                   sc.found.as<int32_t>(), s));
         OFC_TRY(mark(false, 0, what == 5 || what == 6));
-        if (timed) {
-            OFC_HIP(hipEventSynchronize(e1));
-            float ms = 0;
-            OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-            total += ms;
-        }
+        if (timed) OFC_TRY(ev.add_elapsed(total));
         return OFC_OK;
     };
     for (int w = 0; w < 2; w++) OFC_TRY(run(false));
     for (int i = 0; i < iters; i++) OFC_TRY(run(true));
     OFC_HIP(hipStreamSynchronize(s));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     int e = 0;
     OFC_HIP(hipMemcpy(&e, err, sizeof(int), hipMemcpyDeviceToHost));
     if (e != 0) {

@@ -1,6 +1,7 @@
 // fb_check_api.cpp -- C ABI of libofc.so, part 9: the forward-backward check of a flow field (fb_check.hip) on device and host
 // buffers, its mask on key maps and weights, the reversed copy of a clip, the host form of its check and its measurement hook.
 #include "fb_check.h"
+#include "host_util.h"
 
 #include <mutex>
 
@@ -14,17 +15,7 @@ struct FbScratch {
     std::mutex mu;
 };
 
-FbScratch &scratch_for(int device)
-{
-    static FbScratch *pool = new FbScratch[16];            // intentionally never destroyed (no HIP calls at exit)
-    return pool[device & 15];
-}
-
-int ensure(DevBuf &b, size_t need)
-{
-    if (b.bytes >= need) return OFC_OK;
-    return b.alloc(need);
-}
+FbScratch &scratch_for(int device) { return device_scratch<FbScratch>(device); }
 
 }  // namespace
 
@@ -56,11 +47,11 @@ int ofc_consist(int device, const float *fwd_host, const float *bwd_host, int W,
     FbScratch &sc = scratch_for(device);
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t n = (size_t)W * H * npair;
-    OFC_TRY(ensure(sc.fwd, sizeof(float) * 2 * n));
-    OFC_TRY(ensure(sc.bwd, sizeof(float) * 2 * n));
-    OFC_TRY(ensure(sc.state, n));
-    OFC_TRY(ensure(sc.counts, sizeof(int64_t) * FB_NSTATE * npair));
-    if (resid_host) OFC_TRY(ensure(sc.resid, sizeof(int32_t) * 2 * n));
+    OFC_TRY(reserve(sc.fwd, sizeof(float) * 2 * n));
+    OFC_TRY(reserve(sc.bwd, sizeof(float) * 2 * n));
+    OFC_TRY(reserve(sc.state, n));
+    OFC_TRY(reserve(sc.counts, sizeof(int64_t) * FB_NSTATE * npair));
+    if (resid_host) OFC_TRY(reserve(sc.resid, sizeof(int32_t) * 2 * n));
     OFC_HIP(hipMemcpy(sc.fwd.p, fwd_host, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
     OFC_HIP(hipMemcpy(sc.bwd.p, bwd_host, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
     OFC_TRY(launch_fb_check(sc.fwd.as<float>(), sc.bwd.as<float>(), W, H, npair, bwd_reversed != 0, alpha_q, beta_q,
@@ -108,12 +99,12 @@ int ofc_bench_consist(int device, const float *fwd_dev, const float *bwd_dev, in
     FbScratch &sc = scratch_for(device);
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t n = (size_t)W * H * npair;
-    OFC_TRY(ensure(sc.state, n));
-    OFC_TRY(ensure(sc.counts, sizeof(int64_t) * FB_NSTATE * npair));
-    if (what == 1) OFC_TRY(ensure(sc.resid, sizeof(int32_t) * 2 * n));
+    OFC_TRY(reserve(sc.state, n));
+    OFC_TRY(reserve(sc.counts, sizeof(int64_t) * FB_NSTATE * npair));
+    if (what == 1) OFC_TRY(reserve(sc.resid, sizeof(int32_t) * 2 * n));
     if (what == 2) {
-        OFC_TRY(ensure(sc.keys, n));
-        OFC_TRY(ensure(sc.w, sizeof(float) * n));
+        OFC_TRY(reserve(sc.keys, n));
+        OFC_TRY(reserve(sc.w, sizeof(float) * n));
     }
     hipStream_t s = nullptr;
     uint8_t *state = sc.state.as<uint8_t>();
@@ -123,31 +114,25 @@ int ofc_bench_consist(int device, const float *fwd_dev, const float *bwd_dev, in
         OFC_HIP(hipMemsetAsync(sc.w.p, 0, sizeof(float) * n, s));
         OFC_TRY(launch_fb_check(fwd_dev, bwd_dev, W, H, npair, false, ALPHA, BETA, state, counts, nullptr, s));
     }
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
+    EventPair ev;
+    OFC_TRY(ev.create());
     double total = 0;
     auto run = [&](bool timed) -> int {
-        if (timed) OFC_HIP(hipEventRecord(e0, s));
+        if (timed) OFC_HIP(hipEventRecord(ev.e0, s));
         if (what == 2)
             OFC_TRY(launch_consist_mask(state, (int64_t)n, 1 << OFC_CONSIST_OK, sc.keys.as<uint8_t>(), sc.w.as<float>(), s));
         else
             OFC_TRY(launch_fb_check(fwd_dev, bwd_dev, W, H, npair, false, ALPHA, BETA, state, counts,
                                     what == 1 ? sc.resid.as<int32_t>() : nullptr, s));
         if (timed) {
-            OFC_HIP(hipEventRecord(e1, s));
-            OFC_HIP(hipEventSynchronize(e1));
-            float ms = 0;
-            OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-            total += ms;
+            OFC_HIP(hipEventRecord(ev.e1, s));
+            OFC_TRY(ev.add_elapsed(total));
         }
         return OFC_OK;
     };
     for (int w = 0; w < 2; w++) OFC_TRY(run(false));
     for (int i = 0; i < iters; i++) OFC_TRY(run(true));
     OFC_HIP(hipStreamSynchronize(s));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *ms_per_run = (float)(total / iters);
     return OFC_OK;
 }

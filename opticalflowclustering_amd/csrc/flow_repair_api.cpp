@@ -2,6 +2,7 @@
 // (flow_repair.hip) on device and host buffers, the host form of its check, its tile shape and its measurement hook.  The
 // stream's side of it is in stream_api.cpp.
 #include "flow_repair.h"
+#include "host_util.h"
 
 #include <mutex>
 
@@ -16,25 +17,15 @@ struct RepairBuffers {
     std::mutex mu;
 };
 
-RepairBuffers &scratch_for(int device)
-{
-    static RepairBuffers *pool = new RepairBuffers[16];    // intentionally never destroyed (no HIP calls at exit)
-    return pool[device & 15];
-}
-
-int ensure(DevBuf &b, size_t need)
-{
-    if (b.bytes >= need) return OFC_OK;
-    return b.alloc(need);
-}
+RepairBuffers &scratch_for(int device) { return device_scratch<RepairBuffers>(device); }
 
 // the snapshots a launch of this shape needs: b only with more than two sweeps, filled only where the caller keeps none
 int ensure_scratch(RepairBuffers &sc, int W, int H, int npair, int sweeps, bool own_filled, RepairScratch &out)
 {
     out.chunk = repair_chunk_pairs(W, H, npair);
-    OFC_TRY(ensure(sc.a, repair_field_bytes(W, H, out.chunk)));
-    if (sweeps > 2) OFC_TRY(ensure(sc.b, repair_field_bytes(W, H, out.chunk)));
-    if (own_filled) OFC_TRY(ensure(sc.filled, repair_filled_bytes(W, H, out.chunk)));
+    OFC_TRY(reserve(sc.a, repair_field_bytes(W, H, out.chunk)));
+    if (sweeps > 2) OFC_TRY(reserve(sc.b, repair_field_bytes(W, H, out.chunk)));
+    if (own_filled) OFC_TRY(reserve(sc.filled, repair_filled_bytes(W, H, out.chunk)));
     out.a = sc.a.as<float>(), out.b = sc.b.as<float>(), out.filled = sc.filled.as<uint8_t>();
     return OFC_OK;
 }
@@ -89,10 +80,10 @@ int ofc_repair(int device, const float *flow_host, const uint8_t *state_host, in
     const size_t n = (size_t)W * H * npair, fbytes = repair_field_bytes(W, H, npair);
     RepairScratch rs;
     OFC_TRY(ensure_scratch(sc, W, H, npair, rounds + smooth, false, rs));
-    OFC_TRY(ensure(sc.flow, fbytes));
-    OFC_TRY(ensure(sc.work, n));                            // the whole clip's filled map
-    OFC_TRY(ensure(sc.counts, sizeof(int64_t) * REPAIR_NCOUNT * npair));
-    if (state_host) OFC_TRY(ensure(sc.state, n));
+    OFC_TRY(reserve(sc.flow, fbytes));
+    OFC_TRY(reserve(sc.work, n));                            // the whole clip's filled map
+    OFC_TRY(reserve(sc.counts, sizeof(int64_t) * REPAIR_NCOUNT * npair));
+    if (state_host) OFC_TRY(reserve(sc.state, n));
     OFC_HIP(hipMemcpy(sc.flow.p, flow_host, fbytes, hipMemcpyHostToDevice));
     if (state_host) OFC_HIP(hipMemcpy(sc.state.p, state_host, n, hipMemcpyHostToDevice));
     // in place on the uploaded field and, where asked for, on the uploaded state map
@@ -120,31 +111,25 @@ int ofc_bench_repair(int device, const float *flow_dev, const uint8_t *state_dev
     std::lock_guard<std::mutex> lock(sc.mu);
     RepairScratch rs;
     OFC_TRY(ensure_scratch(sc, W, H, npair, 1, false, rs));
-    OFC_TRY(ensure(sc.work, repair_field_bytes(W, H, npair)));
-    OFC_TRY(ensure(sc.counts, sizeof(int64_t) * REPAIR_NCOUNT * npair));
+    OFC_TRY(reserve(sc.work, repair_field_bytes(W, H, npair)));
+    OFC_TRY(reserve(sc.counts, sizeof(int64_t) * REPAIR_NCOUNT * npair));
     hipStream_t s = nullptr;
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
+    EventPair ev;
+    OFC_TRY(ev.create());
     double total = 0;
     auto run = [&](bool timed) -> int {
-        if (timed) OFC_HIP(hipEventRecord(e0, s));
+        if (timed) OFC_HIP(hipEventRecord(ev.e0, s));
         OFC_TRY(launch_repair(flow_dev, state_dev, W, H, npair, KEEP, radius, rounds, MIN_COUNT, smooth != 0, sc.work.as<float>(), nullptr,
                               nullptr, sc.counts.as<int64_t>(), rs, s));
         if (timed) {
-            OFC_HIP(hipEventRecord(e1, s));
-            OFC_HIP(hipEventSynchronize(e1));
-            float ms = 0;
-            OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-            total += ms;
+            OFC_HIP(hipEventRecord(ev.e1, s));
+            OFC_TRY(ev.add_elapsed(total));
         }
         return OFC_OK;
     };
     for (int w = 0; w < 2; w++) OFC_TRY(run(false));
     for (int i = 0; i < iters; i++) OFC_TRY(run(true));
     OFC_HIP(hipStreamSynchronize(s));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *ms_per_run = (float)(total / iters);
     return OFC_OK;
 }

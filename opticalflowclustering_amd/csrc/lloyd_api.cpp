@@ -1,6 +1,7 @@
 // lloyd_api.cpp -- C ABI of libofc.so, part 2: Lloyd k-means drivers (streaming shape).
 // Control flow = sklearn's _kmeans_single_lloyd (_kmeans.py:624-752) around the kernels of
 // lloyd_kernels.hip; see include/ofc.h for the reference call sites.
+#include "host_util.h"
 #include "lloyd_common.h"
 
 #include <algorithm>
@@ -57,7 +58,7 @@ struct LloydScratch {
     {
         const size_t nt = (size_t)(N >> 6), ng = W > 0 ? nt >> 3 : 0;
         const size_t goff = (nt * 40 + 15) & ~(size_t)15, need = goff + ng * 40 + 16;
-        if (tile_block.bytes < need) OFC_TRY(tile_block.alloc(need));
+        OFC_TRY(reserve(tile_block, need));
         char *p = tile_block.as<char>();
         f.box = p;
         f.tsum = p + nt * 16;
@@ -82,11 +83,7 @@ static int prune_policy_for(int dtype, int64_t N, int d, int k)
     return v;
 }
 
-static LloydScratch &scratch_for(int device)
-{
-    static LloydScratch *pool = new LloydScratch[16];   // intentionally never destroyed (no HIP calls at exit)
-    return pool[device & 15];
-}
+static LloydScratch &scratch_for(int device) { return device_scratch<LloydScratch>(device); }
 
 // empty-cluster relocation (_k_means_common.pyx:167-211) on the all-reduced totals `tot`.
 // Returns with `tot` patched on the device (or untouched when the farthest distance is 0).
@@ -212,7 +209,7 @@ static int lloyd_fit_dev(int device, const void *X, int dtype, int64_t N, int d,
     hipStream_t s = sc.stream;
     const int nblocks = lloyd_grid(N);
     if (!labels_dev) {
-        if (sc.labels.bytes < (size_t)std::max<int64_t>(N, 1)) OFC_TRY(sc.labels.alloc((size_t)std::max<int64_t>(N, 1)));
+        OFC_TRY(reserve(sc.labels, (size_t)std::max<int64_t>(N, 1)));
         labels_dev = sc.labels.as<uint8_t>();
     }
     LloydState *st = sc.state.as<LloydState>();
@@ -398,30 +395,6 @@ static int lloyd_predict_dev(int device, const void *X, int dtype, int64_t N, in
     return OFC_OK;
 }
 
-// the measurement hooks: two untimed launches, then the average of `iters` by HIP events on the stream; the events are
-// destroyed whichever way it ends
-template <class F> static int time_launches(hipStream_t s, int iters, F &&launch, float *ms_per_launch)
-{
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto timed = [&]() -> int {
-        OFC_HIP(hipEventCreate(&e0));
-        OFC_HIP(hipEventCreate(&e1));
-        for (int w = 0; w < 2; w++) OFC_TRY(launch());
-        OFC_HIP(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; i++) OFC_TRY(launch());
-        OFC_HIP(hipEventRecord(e1, s));
-        OFC_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-        *ms_per_launch = ms / iters;
-        return OFC_OK;
-    };
-    const int rc = timed();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
-}
-
 static void widen_labels(const uint8_t *src, int64_t N, int32_t *dst)
 {
     for (int64_t i = 0; i < N; i++) dst[i] = src[i];
@@ -455,7 +428,7 @@ int ofc_bench_lloyd_sweep(int device, const float *X_dev, int64_t N, int k, cons
     const int nblocks = lloyd_grid(N);
     LloydFieldBufs tb = {};
     OFC_TRY(sc.tile_bufs(N, 0, tb));
-    if (sc.labels.bytes < (size_t)N) OFC_TRY(sc.labels.alloc((size_t)N));
+    OFC_TRY(reserve(sc.labels, (size_t)N));
     LloydState *st = sc.state.as<LloydState>();
     OFC_HIP(hipMemsetAsync(st, 0, sizeof(LloydState), s));
     double c0[LLOYD_KMAX * LLOYD_DMAX];
@@ -866,11 +839,9 @@ int kpp_seed(int device, const void *X_dev, int dtype, const void *w_dev, int w_
     const int64_t nchunks = kpp_chunks(N);
     const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(nchunks, 4), 2048));
     if (N > 0) {
-        if (sc.kpp_closest.bytes < sizeof(double) * (size_t)N) OFC_TRY(sc.kpp_closest.alloc(sizeof(double) * (size_t)N));
-        if (sc.kpp_cs.bytes < sizeof(double) * 8 * (size_t)nchunks) {
-            OFC_TRY(sc.kpp_cs.alloc(sizeof(double) * 8 * (size_t)nchunks));
-            OFC_TRY(sc.kpp_ss.alloc(sizeof(double) * (size_t)cdiv64(nchunks, 1024)));
-        }
+        OFC_TRY(reserve(sc.kpp_closest, sizeof(double) * (size_t)N));
+        OFC_TRY(reserve(sc.kpp_cs, sizeof(double) * 8 * (size_t)nchunks));
+        OFC_TRY(reserve(sc.kpp_ss, sizeof(double) * (size_t)cdiv64(nchunks, 1024)));
     }
     double *closest = sc.kpp_closest.as<double>(), *cs = sc.kpp_cs.as<double>(), *ss = sc.kpp_ss.as<double>();
     const size_t es = dtype_size(dtype);

@@ -1,5 +1,6 @@
 // motion_api.cpp -- C ABI of libofc.so, part 6: per-pair camera motion (motion_model.hip) on device and host buffers, the
 // host forms of its checks and its solve, and its measurement hook.  The streaming ingest's camera is stream_api.cpp's.
+#include "host_util.h"
 #include "motion_model.h"
 
 using namespace ofc;
@@ -208,20 +209,7 @@ int ofc_bench_motion(int device, const float *flow_dev, int W, int H, int npair,
         default: return motion_fit_async(flow_dev, W, H, npair, 2, thr, 3, rec, part, nullptr, nullptr, s);
         }
     };
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
-    for (int w = 0; w < 2; w++) OFC_TRY(run());
-    OFC_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; i++) OFC_TRY(run());
-    OFC_HIP(hipEventRecord(e1, s));
-    OFC_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return OFC_OK;
+    return time_launches(s, iters, run, ms_per_launch);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // ofc_api.cpp -- C ABI of libofc.so, part 1: runtime plumbing and the Farneback flow engine.
 // Declared in include/ofc.h (which cites the reference call each entry point replaces).
 #include "color_common.h"
+#include "host_util.h"
 #include "lloyd_common.h"
 
 #include <cfloat>
@@ -338,7 +339,7 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
                     if (uv_sum_dev && k == 0 && l == L - 1 && plan[l] == 1 && f->prm.winsize == 15 && !(f->w3 && g.w >= f->w3_min_w)) {
                         // the field's column sums ride in the epilogue of the iteration that writes it
                         const size_t need = (size_t)flow_iter_max_grid(g.w, g.h, npair, f->prm.winsize) * 2;
-                        if (f->uv_scratch.bytes < need * sizeof(double)) OFC_TRY(f->uv_scratch.alloc(need * sizeof(double)));
+                        OFC_TRY(reserve(f->uv_scratch, need * sizeof(double)));
                         // the launch is told what the buffer holds, not what this call needs: its own check then guards the records
                         OFC_TRY(launch_flow_iter(R, strideR, cur, nxt, npair, g.w, g.h, f->prm.winsize, s, nullptr, 0, 0, 1.f,
                                                  uv_sum_dev, f->uv_scratch.as<double>(), f->uv_scratch.bytes / sizeof(double)));
@@ -374,7 +375,7 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
         const int64_t N = (int64_t)npair * W * H;
         const int max_blocks = 1024;    // the scratch is sized for the most records a sweep writes (16 KiB), whatever this call needs
         const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(N / 4, 256), max_blocks));
-        if (f->uv_scratch.bytes < sizeof(double) * 2 * max_blocks) OFC_TRY(f->uv_scratch.alloc(sizeof(double) * 2 * max_blocks));
+        OFC_TRY(reserve(f->uv_scratch, sizeof(double) * 2 * max_blocks));
         OFC_TRY(launch_lloyd_colstats(flow_dev, OFC_F32, N, 2, nullptr, 0, f->uv_scratch.as<double>(), nblocks, s));
         OFC_TRY(launch_reduce_records(f->uv_scratch.as<double>(), nblocks, 2, uv_sum_dev, s));
     }
@@ -839,17 +840,15 @@ int ofc_bench_flow_iters(int device, int W, int H, int n_pairs, int reps, int mo
     OFC_TRY(R.alloc(sizeof(float) * 5 * P * nf));
     OFC_TRY(fa.alloc(sizeof(float) * 2 * P * n_pairs));
     OFC_TRY(fb.alloc(sizeof(float) * 2 * P * n_pairs));
-    hipStream_t s;
-    OFC_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    ScopedStream own;
+    OFC_TRY(own.create());
+    hipStream_t s = own.s;
     OFC_TRY(ofc_synth_frames_dev(device, fr.as<uint8_t>(), W, H, nf, 0, 0));
     OFC_HIP(hipDeviceSynchronize());
     OFC_TRY(launch_polyexp_u8(fr.as<uint8_t>(), R.as<float>(), nf, W, H, pc, s));
     OFC_HIP(hipMemsetAsync(fb.p, 0, sizeof(float) * 2 * P * n_pairs, s));
     // a realistic flow_in: one iteration from zero flow
     OFC_TRY(launch_flow_iter(R.as<float>(), 5 * P, fb.as<float>(), fa.as<float>(), n_pairs, W, H, 15, s));
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
     if (mode == 3) {            // diagnostic: the stamped build of k_flow_iter, phase shares printed to stdout
         int grid = 0;
         OFC_TRY(launch_flow_iter_stamped(R.as<float>(), 5 * P, fa.as<float>(), fb.as<float>(), n_pairs, W, H, s, nullptr, &grid));
@@ -870,7 +869,6 @@ int ofc_bench_flow_iters(int device, int W, int H, int n_pairs, int reps, int mo
         for (int i = 0; i < 8; i++) printf("  %-42s %5.1f %%\n", name[i], 100.0 * tot[i] / all);
         fflush(stdout);
         *ms_out = 0.f;
-        (void)hipStreamDestroy(s);
         return OFC_OK;
     }
     auto two = [&]() -> int {
@@ -883,18 +881,7 @@ int ofc_bench_flow_iters(int device, int W, int H, int n_pairs, int reps, int mo
         // second iteration in place of the pair's scratch: fb -> fa would overwrite the input; write a third pass back to fb
         return launch_flow_iter(R.as<float>(), 5 * P, fb.as<float>(), fa.as<float>(), n_pairs, W, H, 15, s);
     };
-    OFC_TRY(two());
-    OFC_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < reps; i++) OFC_TRY(two());
-    OFC_HIP(hipEventRecord(e1, s));
-    OFC_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_out = ms / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipStreamDestroy(s);
-    return OFC_OK;
+    return time_launches(s, reps, two, ms_out, 1);          // one warm-up call of the pair
 }
 
 // bench hook: polyexp over n_images distinct resident images, HIP events on the launch stream
@@ -920,23 +907,11 @@ int ofc_bench_polyexp(int device, int W, int H, int n_images, int iters, int row
             OFC_HIP(hipMemcpy(I.as<float>() + (size_t)im * P, h.data(), sizeof(float) * P, hipMemcpyHostToDevice));
         }
     }
-    hipStream_t s;
-    OFC_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
-    for (int w = 0; w < 2; w++) OFC_TRY(launch_polyexp(I.as<float>(), R.as<float>(), n_images, W, H, pc, rows_per_block, s, true));
-    OFC_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; i++) OFC_TRY(launch_polyexp(I.as<float>(), R.as<float>(), n_images, W, H, pc, rows_per_block, s, true));
-    OFC_HIP(hipEventRecord(e1, s));
-    OFC_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipStreamDestroy(s);
-    return OFC_OK;
+    ScopedStream own;
+    OFC_TRY(own.create());
+    hipStream_t s = own.s;
+    auto launch = [&]() -> int { return launch_polyexp(I.as<float>(), R.as<float>(), n_images, W, H, pc, rows_per_block, s, true); };
+    return time_launches(s, iters, launch, ms_per_launch);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // photo_check_api.cpp -- C ABI of libofc.so, part 10: the photometric check of a flow field against its frames
 // (photo_check.hip) on device and host buffers, the host form of its check and its measurement hook.  The stream's side of it
 // is in stream_api.cpp.
+#include "host_util.h"
 #include "photo_check.h"
 
 #include <mutex>
@@ -15,17 +16,7 @@ struct PhotoScratch {
     std::mutex mu;
 };
 
-PhotoScratch &scratch_for(int device)
-{
-    static PhotoScratch *pool = new PhotoScratch[16];      // intentionally never destroyed (no HIP calls at exit)
-    return pool[device & 15];
-}
-
-int ensure(DevBuf &b, size_t need)
-{
-    if (b.bytes >= need) return OFC_OK;
-    return b.alloc(need);
-}
+PhotoScratch &scratch_for(int device) { return device_scratch<PhotoScratch>(device); }
 
 }  // namespace
 
@@ -55,11 +46,11 @@ int ofc_photo(int device, const uint8_t *frames_host, const float *fwd_host, int
     PhotoScratch &sc = scratch_for(device);
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t P = (size_t)W * H, n = P * npair;
-    OFC_TRY(ensure(sc.frames, P * (npair + 1)));
-    OFC_TRY(ensure(sc.fwd, sizeof(float) * 2 * n));
-    OFC_TRY(ensure(sc.state, n));
-    OFC_TRY(ensure(sc.stats, sizeof(int64_t) * PHOTO_NSTAT * npair));
-    if (warped_host) OFC_TRY(ensure(sc.warped, sizeof(uint16_t) * n));
+    OFC_TRY(reserve(sc.frames, P * (npair + 1)));
+    OFC_TRY(reserve(sc.fwd, sizeof(float) * 2 * n));
+    OFC_TRY(reserve(sc.state, n));
+    OFC_TRY(reserve(sc.stats, sizeof(int64_t) * PHOTO_NSTAT * npair));
+    if (warped_host) OFC_TRY(reserve(sc.warped, sizeof(uint16_t) * n));
     OFC_HIP(hipMemcpy(sc.frames.p, frames_host, P * (npair + 1), hipMemcpyHostToDevice));
     OFC_HIP(hipMemcpy(sc.fwd.p, fwd_host, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
     OFC_TRY(launch_photo_check(sc.frames.as<uint8_t>(), sc.fwd.as<float>(), W, H, npair, tau_q, kappa_q, sc.state.as<uint8_t>(),
@@ -82,32 +73,26 @@ int ofc_bench_photo(int device, const uint8_t *frames_dev, const float *fwd_dev,
     PhotoScratch &sc = scratch_for(device);
     std::lock_guard<std::mutex> lock(sc.mu);
     const size_t n = (size_t)W * H * npair;
-    OFC_TRY(ensure(sc.state, n));
-    OFC_TRY(ensure(sc.stats, sizeof(int64_t) * PHOTO_NSTAT * npair));
-    if (what == 1) OFC_TRY(ensure(sc.warped, sizeof(uint16_t) * n));
+    OFC_TRY(reserve(sc.state, n));
+    OFC_TRY(reserve(sc.stats, sizeof(int64_t) * PHOTO_NSTAT * npair));
+    if (what == 1) OFC_TRY(reserve(sc.warped, sizeof(uint16_t) * n));
     hipStream_t s = nullptr;
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
+    EventPair ev;
+    OFC_TRY(ev.create());
     double total = 0;
     auto run = [&](bool timed) -> int {
-        if (timed) OFC_HIP(hipEventRecord(e0, s));
+        if (timed) OFC_HIP(hipEventRecord(ev.e0, s));
         OFC_TRY(launch_photo_check(frames_dev, fwd_dev, W, H, npair, TAU, KAPPA, sc.state.as<uint8_t>(), sc.stats.as<int64_t>(),
                                    what == 1 ? sc.warped.as<uint16_t>() : nullptr, s));
         if (timed) {
-            OFC_HIP(hipEventRecord(e1, s));
-            OFC_HIP(hipEventSynchronize(e1));
-            float ms = 0;
-            OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-            total += ms;
+            OFC_HIP(hipEventRecord(ev.e1, s));
+            OFC_TRY(ev.add_elapsed(total));
         }
         return OFC_OK;
     };
     for (int w = 0; w < 2; w++) OFC_TRY(run(false));
     for (int i = 0; i < iters; i++) OFC_TRY(run(true));
     OFC_HIP(hipStreamSynchronize(s));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *ms_per_run = (float)(total / iters);
     return OFC_OK;
 }

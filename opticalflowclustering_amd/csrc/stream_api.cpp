@@ -18,6 +18,7 @@
 #include "color_common.h"
 #include "fb_check.h"
 #include "flow_repair.h"
+#include "host_util.h"
 #include "lloyd_common.h"
 #include "motion_model.h"
 #include "photo_check.h"
@@ -25,6 +26,42 @@
 #include <memory>
 
 using namespace ofc;
+
+// A table with one row per frame pair of the clip, on the device.  It starts at 256 pairs and doubles when a batch would
+// not fit; the rows written so far move to the new buffer behind the compute stream.  Every table grows on its own, so a
+// failed allocation leaves each of them either as it was or grown, never half of a group.
+struct PairTable {
+    DevBuf buf;
+    size_t per = 0, cap = 0;           // bytes per pair; pairs there is room for
+    explicit PairTable(size_t bytes_per_pair = 0) : per(bytes_per_pair) {}
+    int ensure(int need_pairs, int have_pairs, hipStream_t compute)
+    {
+        if ((size_t)need_pairs <= cap) return OFC_OK;
+        const size_t grown = std::max<size_t>(need_pairs, cap ? cap * 2 : 256);
+        DevBuf nb;
+        OFC_TRY(nb.alloc(grown * per));
+        if (buf.p && have_pairs) {
+            OFC_HIP(hipStreamSynchronize(compute));
+            OFC_HIP(hipMemcpy(nb.p, buf.p, (size_t)have_pairs * per, hipMemcpyDeviceToDevice));
+        }
+        std::swap(buf.p, nb.p);
+        std::swap(buf.bytes, nb.bytes);
+        cap = grown;
+        return OFC_OK;
+    }
+    // the table is empty and may change its layout: start over
+    void reset()
+    {
+        buf.release();
+        cap = 0;
+    }
+    void reset(size_t bytes_per_pair)
+    {
+        reset();
+        per = bytes_per_pair;
+    }
+    template <class T> T *row(size_t pair) const { return reinterpret_cast<T *>(static_cast<char *>(buf.p) + pair * per); }
+};
 
 struct ofc_stream {
     int device = 0, W = 0, H = 0, batch = 0, rows = 0, cols = 0;
@@ -39,15 +76,13 @@ struct ofc_stream {
         bool busy = false;             // a batch of this slot is in flight
     } slot[2];
     int cur = 0;
-    DevBuf cells;                      // [max_pairs][rows*cols][2] f32, grows
-    size_t cells_cap = 0;              // pairs
+    PairTable cells;                   // [rows*cols][2] f32 per pair
     int pairs_submitted = 0;
     // the model, when there is one (k > 0): its LloydState on the device, and what it says about every pair so far
     int k = 0;
     bool with_sums = false;
     DevBuf model;                      // LloydState
-    DevBuf counts, sums;               // [max_pairs][rows*cols][k] int32, [...][k][2] f64 (with_sums): grow with `cells`
-    size_t clusters_cap = 0;           // pairs
+    PairTable counts, sums;            // [rows*cols][k] int32 and, with_sums, [rows*cols][k][2] f64 per pair
     // the (u,v) histogram, when there is one (hist_bins > 0): every batch adds to it, a finish leaves it alone
     int hist_bins = 0;
     float hist_range = 0.f;
@@ -55,199 +90,72 @@ struct ofc_stream {
     // the camera, when there is one (cam_kind > 0): every pair's fit, kept past the finish until the next clip's batches overwrite it
     int cam_kind = 0, cam_T = 0;
     double cam_thr[8] = {};
-    DevBuf cam_rec, cam_partial;       // MotionRec [max_pairs], grows with `cells`; the moment kernel's partials of a batch
-    size_t cam_cap = 0;                // pairs
+    PairTable cam_rec{sizeof(MotionRec)};
+    DevBuf cam_partial;                // the moment kernel's partials of a batch
     int cam_pairs = 0;                 // pairs of the last finish: what ofc_stream_read_camera delivers
     // the blobs, when there are any (blob_conn > 0): every pair's table, kept past the finish like the camera's fits
     int blob_conn = 0, blob_min_area = 1, blob_max = 0;
     float blob_thr = 0.f;
     DevBuf blob_keys, blob_labels, blob_words, blob_err;   // one batch's key map, label map and area / slot words; the error word
-    DevBuf blob_table, blob_found;     // [max_pairs][blob_max][12] int64 and [max_pairs] int32: grow with `cells`
-    size_t blob_cap = 0;               // pairs
+    PairTable blob_table, blob_found{sizeof(int32_t)};     // [blob_max][12] int64 and one int32 per pair
     int blob_pairs = 0;                // pairs of the last finish: what ofc_stream_read_blobs delivers
     // the blob links, when there are any (link_max > 0; only with blobs): transition g leads from pair g to pair g + 1 of the clip
     int link_max = 0;
     DevBuf link_moves, link_areas;     // one batch's moves and areas at the roots, int32 [batch][H][W] each
     DevBuf link_carry;                 // the previous batch's last pair: label map, moves, areas, int32 [3][H][W]
-    DevBuf link_keys, link_votes, link_counters;   // [max_pairs][cap] uint64, [max_pairs][cap] int32, [max_pairs] int32: grow
-    size_t link_cap = 0;               // transitions
+    // [capacity] uint64, [capacity] int32 and one int32 per transition; sized by pairs (one transition fewer, never more)
+    PairTable link_keys, link_votes, link_counters{sizeof(int32_t)};
     // the photometric check, when there is one (photo_on): every pair's stats, kept past the finish like the camera's fits
     bool photo_on = false;
     int photo_tau = 0, photo_kappa = 0, photo_keep = 0;
     DevBuf photo_state;                // one batch's state map, u8 [batch][H][W]
-    DevBuf photo_stats;                // [max_pairs][5] int64: grows with `cells`
-    size_t photo_cap = 0;              // pairs
+    PairTable photo_stats{sizeof(int64_t) * PHOTO_NSTAT};
     int photo_pairs = 0;               // pairs of the last finish: what ofc_stream_read_photo delivers
     // the repair, when there is one (repair_on): every pair's counts, kept past the finish like the photometric stats
     bool repair_on = false;
     int repair_keep = 0, repair_radius = 0, repair_rounds = 0, repair_min_count = 0, repair_smooth = 0;
     DevBuf repair_a, repair_b, repair_filled;   // the snapshots and the filled map of a chunk of a batch (RepairScratch)
-    DevBuf repair_counts;              // [max_pairs][3] int64: grows with `cells`
-    size_t repair_cap = 0;             // pairs
+    PairTable repair_counts{sizeof(int64_t) * REPAIR_NCOUNT};
     int repair_pairs = 0;              // pairs of the last finish: what ofc_stream_read_repair delivers
 };
 
 namespace {
 
-int ensure_cells(ofc_stream *s, int need_pairs)
+// entry points that set a stage or read its results need a stream with nothing packed, in flight or undelivered
+int require_idle(const ofc_stream *s, const char *what)
 {
-    if ((size_t)need_pairs <= s->cells_cap) return OFC_OK;
-    size_t cap = std::max<size_t>(need_pairs, s->cells_cap ? s->cells_cap * 2 : 256);
-    DevBuf nb;
-    const size_t per = sizeof(float) * 2 * s->rows * s->cols;
-    OFC_TRY(nb.alloc(cap * per));
-    if (s->cells.p) {
-        OFC_HIP(hipStreamSynchronize(s->compute));
-        OFC_HIP(hipMemcpy(nb.p, s->cells.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
-    }
-    std::swap(s->cells.p, nb.p);
-    std::swap(s->cells.bytes, nb.bytes);
-    s->cells_cap = cap;
+    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
+                "the stream holds frames or undelivered results: %s", what);
     return OFC_OK;
 }
 
-// room for the counts (and sums) of need_pairs pairs: same growth as ensure_cells, what was counted so far is kept
-int ensure_clusters(ofc_stream *s, int need_pairs)
+// the tail of a finish: the clip's pair count goes to every stage whose results outlive it, and the next clip starts at 0
+void deliver(ofc_stream *s)
 {
-    if ((size_t)need_pairs <= s->clusters_cap) return OFC_OK;
-    const size_t cap = std::max<size_t>(need_pairs, s->clusters_cap ? s->clusters_cap * 2 : 256);
-    const size_t per = sizeof(int32_t) * s->rows * s->cols * s->k;
-    DevBuf nc, ns;
-    OFC_TRY(nc.alloc(cap * per));
-    if (s->with_sums) OFC_TRY(ns.alloc(cap * per * 4));
-    if (s->counts.p && s->pairs_submitted) {
-        OFC_HIP(hipStreamSynchronize(s->compute));
-        OFC_HIP(hipMemcpy(nc.p, s->counts.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
-        if (s->with_sums) OFC_HIP(hipMemcpy(ns.p, s->sums.p, (size_t)s->pairs_submitted * per * 4, hipMemcpyDeviceToDevice));
-    }
-    std::swap(s->counts.p, nc.p);
-    std::swap(s->counts.bytes, nc.bytes);
-    std::swap(s->sums.p, ns.p);
-    std::swap(s->sums.bytes, ns.bytes);
-    s->clusters_cap = cap;
-    return OFC_OK;
-}
-
-// room for the camera fits of need_pairs pairs: same growth as ensure_cells, what was fitted so far is kept
-int ensure_camera(ofc_stream *s, int need_pairs)
-{
-    if ((size_t)need_pairs <= s->cam_cap) return OFC_OK;
-    const size_t cap = std::max<size_t>(need_pairs, s->cam_cap ? s->cam_cap * 2 : 256);
-    DevBuf nb;
-    OFC_TRY(nb.alloc(cap * sizeof(MotionRec)));
-    if (s->cam_rec.p && s->pairs_submitted) {
-        OFC_HIP(hipStreamSynchronize(s->compute));
-        OFC_HIP(hipMemcpy(nb.p, s->cam_rec.p, (size_t)s->pairs_submitted * sizeof(MotionRec), hipMemcpyDeviceToDevice));
-    }
-    std::swap(s->cam_rec.p, nb.p);
-    std::swap(s->cam_rec.bytes, nb.bytes);
-    s->cam_cap = cap;
-    return OFC_OK;
-}
-
-// room for the blob tables of need_pairs pairs: same growth as ensure_camera, what was found so far is kept
-int ensure_blobs(ofc_stream *s, int need_pairs)
-{
-    if ((size_t)need_pairs <= s->blob_cap) return OFC_OK;
-    const size_t cap = std::max<size_t>(need_pairs, s->blob_cap ? s->blob_cap * 2 : 256);
-    const size_t per = sizeof(int64_t) * BLOB_NF * s->blob_max;
-    DevBuf nt, nf;
-    OFC_TRY(nt.alloc(cap * per));
-    OFC_TRY(nf.alloc(cap * sizeof(int32_t)));
-    if (s->blob_table.p && s->pairs_submitted) {
-        OFC_HIP(hipStreamSynchronize(s->compute));
-        OFC_HIP(hipMemcpy(nt.p, s->blob_table.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
-        OFC_HIP(hipMemcpy(nf.p, s->blob_found.p, (size_t)s->pairs_submitted * sizeof(int32_t), hipMemcpyDeviceToDevice));
-    }
-    std::swap(s->blob_table.p, nt.p);
-    std::swap(s->blob_table.bytes, nt.bytes);
-    std::swap(s->blob_found.p, nf.p);
-    std::swap(s->blob_found.bytes, nf.bytes);
-    s->blob_cap = cap;
-    return OFC_OK;
-}
-
-// room for the link tables of need_pairs pairs (one transition fewer, never more): same growth as ensure_blobs, what was
-// voted so far is kept
-int ensure_links(ofc_stream *s, int need_pairs)
-{
-    if ((size_t)need_pairs <= s->link_cap) return OFC_OK;
-    const size_t cap = std::max<size_t>(need_pairs, s->link_cap ? s->link_cap * 2 : 256);
-    const size_t slots = blob_link_capacity(s->link_max);
-    DevBuf nk, nv, nc;
-    OFC_TRY(nk.alloc(cap * slots * sizeof(uint64_t)));
-    OFC_TRY(nv.alloc(cap * slots * sizeof(int32_t)));
-    OFC_TRY(nc.alloc(cap * sizeof(int32_t)));
-    if (s->link_keys.p && s->pairs_submitted) {
-        const size_t have = (size_t)s->pairs_submitted;
-        OFC_HIP(hipStreamSynchronize(s->compute));
-        OFC_HIP(hipMemcpy(nk.p, s->link_keys.p, have * slots * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-        OFC_HIP(hipMemcpy(nv.p, s->link_votes.p, have * slots * sizeof(int32_t), hipMemcpyDeviceToDevice));
-        OFC_HIP(hipMemcpy(nc.p, s->link_counters.p, have * sizeof(int32_t), hipMemcpyDeviceToDevice));
-    }
-    std::swap(s->link_keys.p, nk.p);
-    std::swap(s->link_keys.bytes, nk.bytes);
-    std::swap(s->link_votes.p, nv.p);
-    std::swap(s->link_votes.bytes, nv.bytes);
-    std::swap(s->link_counters.p, nc.p);
-    std::swap(s->link_counters.bytes, nc.bytes);
-    s->link_cap = cap;
-    return OFC_OK;
-}
-
-// room for the photometric stats of need_pairs pairs: same growth as ensure_camera, what was checked so far is kept
-int ensure_photo(ofc_stream *s, int need_pairs)
-{
-    if ((size_t)need_pairs <= s->photo_cap) return OFC_OK;
-    const size_t cap = std::max<size_t>(need_pairs, s->photo_cap ? s->photo_cap * 2 : 256);
-    const size_t per = sizeof(int64_t) * PHOTO_NSTAT;
-    DevBuf nb;
-    OFC_TRY(nb.alloc(cap * per));
-    if (s->photo_stats.p && s->pairs_submitted) {
-        OFC_HIP(hipStreamSynchronize(s->compute));
-        OFC_HIP(hipMemcpy(nb.p, s->photo_stats.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
-    }
-    std::swap(s->photo_stats.p, nb.p);
-    std::swap(s->photo_stats.bytes, nb.bytes);
-    s->photo_cap = cap;
-    return OFC_OK;
-}
-
-// room for the repair counts of need_pairs pairs: same growth as ensure_photo, what was counted so far is kept
-int ensure_repair(ofc_stream *s, int need_pairs)
-{
-    if ((size_t)need_pairs <= s->repair_cap) return OFC_OK;
-    const size_t cap = std::max<size_t>(need_pairs, s->repair_cap ? s->repair_cap * 2 : 256);
-    const size_t per = sizeof(int64_t) * REPAIR_NCOUNT;
-    DevBuf nb;
-    OFC_TRY(nb.alloc(cap * per));
-    if (s->repair_counts.p && s->pairs_submitted) {
-        OFC_HIP(hipStreamSynchronize(s->compute));
-        OFC_HIP(hipMemcpy(nb.p, s->repair_counts.p, (size_t)s->pairs_submitted * per, hipMemcpyDeviceToDevice));
-    }
-    std::swap(s->repair_counts.p, nb.p);
-    std::swap(s->repair_counts.bytes, nb.bytes);
-    s->repair_cap = cap;
-    return OFC_OK;
+    s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
+    s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
+    s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
+    s->repair_pairs = s->repair_on ? s->pairs_submitted : 0;
+    s->pairs_submitted = 0;
 }
 
 // Behind a batch's label maps: its areas, then the votes of the transition from the carried pair (when the clip has one
 // before this batch) and of the batch's inner transitions; then the batch's last pair becomes the carried one.
 int submit_links(ofc_stream *s, const int32_t *labels, int npair)
 {
-    const size_t P = (size_t)s->W * s->H, slots = blob_link_capacity(s->link_max);
+    const size_t P = (size_t)s->W * s->H;
     const int base = s->pairs_submitted, first = base > 0 ? base - 1 : 0, ntrans = base + npair - 1 - first;
     const int32_t *moves = s->link_moves.as<int32_t>();
     int32_t *areas = s->link_areas.as<int32_t>(), *carry = s->link_carry.as<int32_t>();
-    uint64_t *keys = s->link_keys.as<uint64_t>();
-    int32_t *votes = s->link_votes.as<int32_t>(), *counters = s->link_counters.as<int32_t>();
+    const PairTable &keys = s->link_keys, &votes = s->link_votes, &counters = s->link_counters;
     OFC_TRY(launch_blob_area(labels, s->W, s->H, npair, areas, s->compute));
-    OFC_TRY(launch_blob_links_clear(s->link_max, ntrans, keys + first * slots, votes + first * slots, counters + first, s->compute));
+    OFC_TRY(launch_blob_links_clear(s->link_max, ntrans, keys.row<uint64_t>(first), votes.row<int32_t>(first),
+                                    counters.row<int32_t>(first), s->compute));
     if (base > 0)
         OFC_TRY(launch_blob_links(carry, carry + P, carry + 2 * P, labels, areas, s->W, s->H, 1, s->blob_min_area, s->link_max,
-                                  keys + first * slots, votes + first * slots, counters + first, s->compute));
+                                  keys.row<uint64_t>(first), votes.row<int32_t>(first), counters.row<int32_t>(first), s->compute));
     OFC_TRY(launch_blob_links(labels, moves, areas, labels + P, areas + P, s->W, s->H, npair - 1, s->blob_min_area, s->link_max,
-                              keys + (size_t)base * slots, votes + (size_t)base * slots, counters + base, s->compute));
+                              keys.row<uint64_t>(base), votes.row<int32_t>(base), counters.row<int32_t>(base), s->compute));
     const size_t last = (size_t)(npair - 1) * P, bytes = sizeof(int32_t) * P;
     OFC_HIP(hipMemcpyAsync(carry, labels + last, bytes, hipMemcpyDeviceToDevice, s->compute));
     OFC_HIP(hipMemcpyAsync(carry + P, moves + last, bytes, hipMemcpyDeviceToDevice, s->compute));
@@ -262,13 +170,17 @@ int submit(ofc_stream *s, int i)
     ofc_stream::Slot &sl = s->slot[i];
     const int npair = sl.n_frames - 1;
     const size_t P = (size_t)s->W * s->H;
-    OFC_TRY(ensure_cells(s, s->pairs_submitted + npair));
-    if (s->k) OFC_TRY(ensure_clusters(s, s->pairs_submitted + npair));
-    if (s->cam_kind) OFC_TRY(ensure_camera(s, s->pairs_submitted + npair));
-    if (s->blob_conn) OFC_TRY(ensure_blobs(s, s->pairs_submitted + npair));
-    if (s->link_max) OFC_TRY(ensure_links(s, s->pairs_submitted + npair));
-    if (s->photo_on) OFC_TRY(ensure_photo(s, s->pairs_submitted + npair));
-    if (s->repair_on) OFC_TRY(ensure_repair(s, s->pairs_submitted + npair));
+    const int base = s->pairs_submitted;
+    // room for this batch's rows in the tables of the stages that are on; what the clip has so far is kept
+    auto room = [&](PairTable &t) { return t.ensure(base + npair, base, s->compute); };
+    OFC_TRY(room(s->cells));
+    if (s->k) OFC_TRY(room(s->counts));
+    if (s->with_sums) OFC_TRY(room(s->sums));
+    if (s->cam_kind) OFC_TRY(room(s->cam_rec));
+    if (s->blob_conn) { OFC_TRY(room(s->blob_table)); OFC_TRY(room(s->blob_found)); }
+    if (s->link_max) { OFC_TRY(room(s->link_keys)); OFC_TRY(room(s->link_votes)); OFC_TRY(room(s->link_counters)); }
+    if (s->photo_on) OFC_TRY(room(s->photo_stats));
+    if (s->repair_on) OFC_TRY(room(s->repair_counts));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
@@ -276,8 +188,7 @@ int submit(ofc_stream *s, int i)
     // the photometric check follows the whole flow into the slot's own next frame: before the camera is subtracted
     if (s->photo_on)
         OFC_TRY(launch_photo_check(sl.frames.as<uint8_t>(), sl.flows.as<float>(), s->W, s->H, npair, s->photo_tau, s->photo_kappa,
-                                   s->photo_state.as<uint8_t>(),
-                                   s->photo_stats.as<int64_t>() + (size_t)s->pairs_submitted * PHOTO_NSTAT, nullptr, s->compute));
+                                   s->photo_state.as<uint8_t>(), s->photo_stats.row<int64_t>(base), nullptr, s->compute));
     // the repair takes the check's state map (without a check only invalid vectors are targets) and works in place on both:
     // everything from here on, the moves and the camera included, sees the repaired field and the updated states
     if (s->repair_on) {
@@ -287,24 +198,22 @@ int submit(ofc_stream *s, int i)
         uint8_t *st = s->photo_on ? s->photo_state.as<uint8_t>() : nullptr;
         OFC_TRY(launch_repair(sl.flows.as<float>(), st, s->W, s->H, npair, s->repair_keep, s->repair_radius, s->repair_rounds,
                               s->repair_min_count, s->repair_smooth != 0, sl.flows.as<float>(), nullptr, st,
-                              s->repair_counts.as<int64_t>() + (size_t)s->pairs_submitted * REPAIR_NCOUNT, rs, s->compute));
+                              s->repair_counts.row<int64_t>(base), rs, s->compute));
     }
     // where the pixels go is what the whole flow says: the moves are taken before the camera is subtracted
     if (s->link_max) OFC_TRY(launch_blob_moves(sl.flows.as<float>(), s->W, s->H, npair, s->link_moves.as<int32_t>(), s->compute));
     if (s->cam_kind) {
-        MotionRec *rec = s->cam_rec.as<MotionRec>() + s->pairs_submitted;
+        MotionRec *rec = s->cam_rec.row<MotionRec>(base);
         OFC_TRY(motion_fit_async(sl.flows.as<float>(), s->W, s->H, npair, s->cam_kind, s->cam_thr, s->cam_T, rec,
                                  s->cam_partial.as<int64_t>(), nullptr, nullptr, s->compute));
         OFC_TRY(launch_motion_subtract(sl.flows.as<float>(), sl.flows.as<float>(), s->W, s->H, npair, rec, s->compute));
     }
-    float *dst = s->cells.as<float>() + (size_t)s->pairs_submitted * 2 * s->rows * s->cols;
-    OFC_TRY(launch_grid_cell_mean_flow(sl.flows.as<float>(), s->W, s->H, npair, s->rows, s->cols, dst, s->compute));
-    if (s->k) {
-        const size_t at = (size_t)s->pairs_submitted * s->rows * s->cols * s->k;
+    OFC_TRY(launch_grid_cell_mean_flow(sl.flows.as<float>(), s->W, s->H, npair, s->rows, s->cols, s->cells.row<float>(base),
+                                       s->compute));
+    if (s->k)
         OFC_TRY(launch_grid_assign_counts(sl.flows.as<float>(), s->model.as<LloydState>(), s->W, s->H, npair, s->rows, s->cols,
-                                          s->k, s->counts.as<int32_t>() + at,
-                                          s->with_sums ? s->sums.as<double>() + at * 2 : nullptr, s->compute));
-    }
+                                          s->k, s->counts.row<int32_t>(base),
+                                          s->with_sums ? s->sums.row<double>(base) : nullptr, s->compute));
     if (s->hist_bins)
         OFC_TRY(launch_uv_hist(sl.flows.as<float>(), (int64_t)P * npair, s->hist_bins, s->hist_range, s->hist.as<int64_t>(),
                                s->compute));
@@ -322,9 +231,8 @@ int submit(ofc_stream *s, int i)
         OFC_TRY(launch_blob_seam(keys, s->W, s->H, npair, s->blob_conn, labels, err, s->compute));
         OFC_TRY(launch_blob_flatten(s->W, s->H, npair, labels, err, s->compute));
         OFC_TRY(launch_blob_table(keys, labels, sl.flows.as<float>(), s->W, s->H, npair, s->blob_min_area, s->blob_max,
-                                  s->blob_words.as<int32_t>(),
-                                  s->blob_table.as<int64_t>() + (size_t)s->pairs_submitted * s->blob_max * BLOB_NF,
-                                  s->blob_found.as<int32_t>() + s->pairs_submitted, s->compute));
+                                  s->blob_words.as<int32_t>(), s->blob_table.row<int64_t>(base), s->blob_found.row<int32_t>(base),
+                                  s->compute));
         if (s->link_max) OFC_TRY(submit_links(s, labels, npair));
     }
     OFC_HIP(hipEventRecord(sl.done, s->compute));
@@ -350,6 +258,7 @@ int ofc_stream_create(int device, int W, int H, const ofc_fb_params *p, int batc
     std::unique_ptr<ofc_stream> s(new ofc_stream);
     s->device = device; s->W = W; s->H = H; s->batch = batch_pairs; s->rows = rows; s->cols = cols;
     OFC_TRY(ofc_flow_create(device, W, H, p, batch_pairs, &s->flow));
+    s->cells.per = sizeof(float) * 2 * rows * cols;
     s->compute = ofc_flow_stream_internal(s->flow);
     OFC_HIP(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
     const size_t P = (size_t)W * H;
@@ -421,14 +330,9 @@ int ofc_stream_finish(ofc_stream_t *s, float *cell_uv, int max_pairs, int *n_pai
     *n_pairs = s->pairs_submitted;
     if (cell_uv) {
         OFC_REQUIRE(max_pairs >= s->pairs_submitted, "cell_uv holds %d pairs, %d produced", max_pairs, s->pairs_submitted);
-        OFC_HIP(hipMemcpy(cell_uv, s->cells.p, sizeof(float) * 2 * s->rows * s->cols * (size_t)s->pairs_submitted,
-                          hipMemcpyDeviceToHost));
+        OFC_HIP(hipMemcpy(cell_uv, s->cells.buf.p, s->cells.per * (size_t)s->pairs_submitted, hipMemcpyDeviceToHost));
     }
-    s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
-    s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
-    s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
-    s->repair_pairs = s->repair_on ? s->pairs_submitted : 0;
-    s->pairs_submitted = 0;
+    deliver(s);
     return OFC_OK;
 }
 
@@ -436,8 +340,7 @@ int ofc_stream_set_model(ofc_stream_t *s, int k, const double *mean, const doubl
 {
     OFC_REQUIRE(s, "null pointer");
     if (k != 0) OFC_TRY(check_uv_model(k, mean, centers_c));
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: set the model on a fresh stream or straight after a finish");
+    OFC_TRY(require_idle(s, "set the model on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
     if (k != 0) {
         LloydState st;
@@ -451,9 +354,9 @@ int ofc_stream_set_model(ofc_stream_t *s, int k, const double *mean, const doubl
         OFC_HIP(hipStreamSynchronize(s->compute));
     }
     if (k != s->k || (with_sums != 0) != s->with_sums) {       // the buffers' layout changes: they are empty, start over
-        s->counts.release();
-        s->sums.release();
-        s->clusters_cap = 0;
+        const size_t per = sizeof(int32_t) * s->rows * s->cols * k;
+        s->counts.reset(per);
+        s->sums.reset(per * 4);                                 // two f64 per count
     }
     s->k = k;
     s->with_sums = k != 0 && with_sums != 0;
@@ -467,20 +370,16 @@ int ofc_stream_finish_clusters(ofc_stream_t *s, float *cell_uv, int32_t *counts,
     OFC_REQUIRE(!sums || s->with_sums, "the model was set without sums");
     OFC_TRY(ensure_device(s->device));
     OFC_TRY(flush(s));
-    const size_t n = (size_t)s->pairs_submitted, cells = (size_t)s->rows * s->cols;
+    const size_t n = (size_t)s->pairs_submitted;
     *n_pairs = s->pairs_submitted;
     if (cell_uv || counts || sums)
         OFC_REQUIRE(max_pairs >= s->pairs_submitted, "the outputs hold %d pairs, %d produced", max_pairs, s->pairs_submitted);
     if (n) {
-        if (cell_uv) OFC_HIP(hipMemcpy(cell_uv, s->cells.p, sizeof(float) * 2 * cells * n, hipMemcpyDeviceToHost));
-        if (counts) OFC_HIP(hipMemcpy(counts, s->counts.p, sizeof(int32_t) * cells * s->k * n, hipMemcpyDeviceToHost));
-        if (sums) OFC_HIP(hipMemcpy(sums, s->sums.p, sizeof(double) * 2 * cells * s->k * n, hipMemcpyDeviceToHost));
+        if (cell_uv) OFC_HIP(hipMemcpy(cell_uv, s->cells.buf.p, s->cells.per * n, hipMemcpyDeviceToHost));
+        if (counts) OFC_HIP(hipMemcpy(counts, s->counts.buf.p, s->counts.per * n, hipMemcpyDeviceToHost));
+        if (sums) OFC_HIP(hipMemcpy(sums, s->sums.buf.p, s->sums.per * n, hipMemcpyDeviceToHost));
     }
-    s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
-    s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
-    s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
-    s->repair_pairs = s->repair_on ? s->pairs_submitted : 0;
-    s->pairs_submitted = 0;
+    deliver(s);
     return OFC_OK;
 }
 
@@ -488,8 +387,7 @@ int ofc_stream_set_histogram(ofc_stream_t *s, int bins, float range)
 {
     OFC_REQUIRE(s, "null pointer");
     if (bins != 0) OFC_TRY(uv_hist_check(bins, range));
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: set the histogram on a fresh stream or straight after a finish");
+    OFC_TRY(require_idle(s, "set the histogram on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
     if (bins == 0) {
         s->hist.release();
@@ -513,8 +411,7 @@ int ofc_stream_read_histogram(ofc_stream_t *s, int64_t *table_host, int reset)
 {
     OFC_REQUIRE(s, "null pointer");
     OFC_REQUIRE(s->hist_bins > 0, "the stream has no histogram (ofc_stream_set_histogram)");
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: read the histogram straight after a finish");
+    OFC_TRY(require_idle(s, "read the histogram straight after a finish"));
     OFC_TRY(ensure_device(s->device));
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
     if (table_host) OFC_HIP(hipMemcpy(table_host, s->hist.p, s->hist.bytes, hipMemcpyDeviceToHost));
@@ -529,14 +426,12 @@ int ofc_stream_set_camera(ofc_stream_t *s, int kind, const double *thresholds, i
 {
     OFC_REQUIRE(s, "null pointer");
     if (kind != 0) OFC_TRY(motion_fit_check(s->W, s->H, kind, thresholds, T));
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: set the camera on a fresh stream or straight after a finish");
+    OFC_TRY(require_idle(s, "set the camera on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
     s->cam_pairs = 0;
     if (kind == 0) {
-        s->cam_rec.release();
+        s->cam_rec.reset();
         s->cam_partial.release();
-        s->cam_cap = 0;
         s->cam_kind = 0;
         s->cam_T = 0;
         return OFC_OK;
@@ -555,14 +450,13 @@ int ofc_stream_read_camera(ofc_stream_t *s, double *models, int *status, int max
 {
     OFC_REQUIRE(s, "null pointer");
     OFC_REQUIRE(s->cam_kind > 0, "the stream has no camera (ofc_stream_set_camera)");
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: read the camera straight after a finish");
+    OFC_TRY(require_idle(s, "read the camera straight after a finish"));
     OFC_REQUIRE(max_pairs >= s->cam_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->cam_pairs);
     OFC_TRY(ensure_device(s->device));
     if (!s->cam_pairs || (!models && !status)) return OFC_OK;
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
     std::vector<MotionRec> rec(s->cam_pairs);
-    OFC_HIP(hipMemcpy(rec.data(), s->cam_rec.p, sizeof(MotionRec) * rec.size(), hipMemcpyDeviceToHost));
+    OFC_HIP(hipMemcpy(rec.data(), s->cam_rec.buf.p, sizeof(MotionRec) * rec.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < s->cam_pairs; i++) {
         if (models) memcpy(models + 6 * (size_t)i, rec[i].p, sizeof(double) * 6);
         if (status) status[i] = rec[i].status;
@@ -570,10 +464,13 @@ int ofc_stream_read_camera(ofc_stream_t *s, double *models, int *status, int max
     return OFC_OK;
 }
 
-static void release_links(ofc_stream *s)
+// slots: the capacity of a transition's table under the links to come, 0 with none
+static void release_links(ofc_stream *s, size_t slots)
 {
-    for (DevBuf *b : {&s->link_moves, &s->link_areas, &s->link_carry, &s->link_keys, &s->link_votes, &s->link_counters}) b->release();
-    s->link_cap = 0;
+    for (DevBuf *b : {&s->link_moves, &s->link_areas, &s->link_carry}) b->release();
+    s->link_keys.reset(slots * sizeof(uint64_t));
+    s->link_votes.reset(slots * sizeof(int32_t));
+    s->link_counters.reset();
     s->link_max = 0;
 }
 
@@ -584,27 +481,26 @@ int ofc_stream_set_blobs(ofc_stream_t *s, int connectivity, float thr, int min_a
         OFC_TRY(blob_check(s->W, s->H, s->batch, connectivity, min_area, max_blobs));
         OFC_REQUIRE(std::isfinite(thr) && thr >= 0, "thr must be finite and >= 0");
     }
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: set the blobs on a fresh stream or straight after a finish");
+    OFC_TRY(require_idle(s, "set the blobs on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
     s->blob_pairs = 0;
-    s->blob_table.release();               // the tables' layout may change: they are empty, start over
-    s->blob_found.release();
-    s->blob_cap = 0;
+    // the tables' layout may change: they are empty, start over
+    s->blob_table.reset(connectivity ? sizeof(int64_t) * BLOB_NF * max_blobs : 0);
+    s->blob_found.reset();
     if (connectivity == 0) {
         s->blob_keys.release();
         s->blob_labels.release();
         s->blob_words.release();
         s->blob_err.release();
         s->blob_conn = 0;
-        release_links(s);
+        release_links(s, 0);
         return OFC_OK;
     }
     const size_t n = (size_t)s->W * s->H * s->batch;
-    if (s->blob_keys.bytes < n) OFC_TRY(s->blob_keys.alloc(n));
-    if (s->blob_labels.bytes < n * sizeof(int32_t)) OFC_TRY(s->blob_labels.alloc(n * sizeof(int32_t)));
-    if (s->blob_words.bytes < n * sizeof(int32_t)) OFC_TRY(s->blob_words.alloc(n * sizeof(int32_t)));
-    if (s->blob_err.bytes < sizeof(int)) OFC_TRY(s->blob_err.alloc(sizeof(int)));
+    OFC_TRY(reserve(s->blob_keys, n));
+    OFC_TRY(reserve(s->blob_labels, n * sizeof(int32_t)));
+    OFC_TRY(reserve(s->blob_words, n * sizeof(int32_t)));
+    OFC_TRY(reserve(s->blob_err, sizeof(int)));
     OFC_HIP(hipMemsetAsync(s->blob_err.p, 0, sizeof(int), s->compute));
     OFC_HIP(hipStreamSynchronize(s->compute));
     s->blob_conn = connectivity;
@@ -618,8 +514,7 @@ int ofc_stream_read_blobs(ofc_stream_t *s, int64_t *table_host, int32_t *n_host,
 {
     OFC_REQUIRE(s, "null pointer");
     OFC_REQUIRE(s->blob_conn > 0, "the stream has no blobs (ofc_stream_set_blobs)");
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: read the blobs straight after a finish");
+    OFC_TRY(require_idle(s, "read the blobs straight after a finish"));
     OFC_REQUIRE(max_pairs >= s->blob_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->blob_pairs);
     OFC_TRY(ensure_device(s->device));
     if (!s->blob_pairs) return OFC_OK;
@@ -631,7 +526,7 @@ int ofc_stream_read_blobs(ofc_stream_t *s, int64_t *table_host, int32_t *n_host,
         set_error("connected components: a capped loop ran out (stages %d); the tables are not valid", e);
         return OFC_EHIP;
     }
-    return blob_table_read(s->blob_table.as<int64_t>(), s->blob_found.as<int32_t>(), s->blob_pairs, s->blob_max, table_host, n_host,
+    return blob_table_read(s->blob_table.row<int64_t>(0), s->blob_found.row<int32_t>(0), s->blob_pairs, s->blob_max, table_host, n_host,
                            found_host);
 }
 
@@ -640,10 +535,9 @@ int ofc_stream_set_blob_links(ofc_stream_t *s, int max_links)
     OFC_REQUIRE(s, "null pointer");
     OFC_REQUIRE(s->blob_conn > 0, "the stream has no blobs (ofc_stream_set_blobs): there is nothing to link");
     if (max_links != 0) OFC_TRY(blob_link_check(s->W, s->H, s->batch, s->blob_min_area, max_links));
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: set the links on a fresh stream or straight after a finish");
+    OFC_TRY(require_idle(s, "set the links on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
-    release_links(s);                      // the tables' layout may change: they are empty, start over
+    release_links(s, max_links ? blob_link_capacity(max_links) : 0);   // the tables' layout may change: they are empty, start over
     s->blob_pairs = 0;                     // ... and so are the blob tables, as after ofc_stream_set_blobs
     if (max_links == 0) return OFC_OK;
     const size_t P = (size_t)s->W * s->H;
@@ -658,15 +552,14 @@ int ofc_stream_read_blob_links(ofc_stream_t *s, int64_t *links_host, int32_t *nl
 {
     OFC_REQUIRE(s, "null pointer");
     OFC_REQUIRE(s->link_max > 0, "the stream has no blob links (ofc_stream_set_blob_links)");
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: read the links straight after a finish");
+    OFC_TRY(require_idle(s, "read the links straight after a finish"));
     const int ntrans = s->blob_pairs > 0 ? s->blob_pairs - 1 : 0;
     OFC_REQUIRE(max_trans >= ntrans, "the outputs hold %d transitions, the last finish delivered %d", max_trans, ntrans);
     OFC_TRY(ensure_device(s->device));
     if (!ntrans) return OFC_OK;
     OFC_REQUIRE(links_host && nlinks_host, "null pointer");
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
-    return blob_links_read(s->link_keys.as<uint64_t>(), s->link_votes.as<int32_t>(), s->link_counters.as<int32_t>(), ntrans,
+    return blob_links_read(s->link_keys.row<uint64_t>(0), s->link_votes.row<int32_t>(0), s->link_counters.row<int32_t>(0), ntrans,
                            s->link_max, links_host, nlinks_host);
 }
 
@@ -677,20 +570,17 @@ int ofc_stream_set_photo(ofc_stream_t *s, int on, int tau_q, int kappa_q, int ke
         OFC_TRY(photo_check(s->W, s->H, s->batch, tau_q, kappa_q));
         OFC_REQUIRE(keep >= 1 && keep < (1 << FB_NSTATE), "keep = %d: a set of the four states, 1 .. 15", keep);
     }
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: set the photometric check on a fresh stream or straight after a "
-                "finish");
+    OFC_TRY(require_idle(s, "set the photometric check on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
     s->photo_pairs = 0;
     if (on == 0) {
         s->photo_state.release();
-        s->photo_stats.release();
-        s->photo_cap = 0;
+        s->photo_stats.reset();
         s->photo_on = false;
         return OFC_OK;
     }
     const size_t n = (size_t)s->W * s->H * s->batch;
-    if (s->photo_state.bytes < n) OFC_TRY(s->photo_state.alloc(n));
+    OFC_TRY(reserve(s->photo_state, n));
     s->photo_on = true;
     s->photo_tau = tau_q;
     s->photo_kappa = kappa_q;
@@ -702,14 +592,13 @@ int ofc_stream_read_photo(ofc_stream_t *s, int64_t *stats_host, int max_pairs)
 {
     OFC_REQUIRE(s, "null pointer");
     OFC_REQUIRE(s->photo_on, "the stream has no photometric check (ofc_stream_set_photo)");
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: read the photometric stats straight after a finish");
+    OFC_TRY(require_idle(s, "read the photometric stats straight after a finish"));
     OFC_REQUIRE(max_pairs >= s->photo_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->photo_pairs);
     OFC_TRY(ensure_device(s->device));
     if (!s->photo_pairs) return OFC_OK;
     OFC_REQUIRE(stats_host, "null pointer");
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
-    OFC_HIP(hipMemcpy(stats_host, s->photo_stats.p, sizeof(int64_t) * PHOTO_NSTAT * (size_t)s->photo_pairs, hipMemcpyDeviceToHost));
+    OFC_HIP(hipMemcpy(stats_host, s->photo_stats.buf.p, s->photo_stats.per * (size_t)s->photo_pairs, hipMemcpyDeviceToHost));
     return OFC_OK;
 }
 
@@ -717,25 +606,23 @@ int ofc_stream_set_repair(ofc_stream_t *s, int on, int keep, int radius, int rou
 {
     OFC_REQUIRE(s, "null pointer");
     if (on != 0) OFC_TRY(repair_check(s->W, s->H, s->batch, keep, radius, rounds, min_count, smooth));
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: set the repair on a fresh stream or straight after a finish");
+    OFC_TRY(require_idle(s, "set the repair on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
     s->repair_pairs = 0;
     if (on == 0) {
         s->repair_a.release();
         s->repair_b.release();
         s->repair_filled.release();
-        s->repair_counts.release();
-        s->repair_cap = 0;
+        s->repair_counts.reset();
         s->repair_on = false;
         return OFC_OK;
     }
     // a batch's chunk: one snapshot, a second with more than two sweeps, and the filled map the state kernel reads
     const int chunk = repair_chunk_pairs(s->W, s->H, s->batch);
     const size_t field = repair_field_bytes(s->W, s->H, chunk), map = repair_filled_bytes(s->W, s->H, chunk);
-    if (s->repair_a.bytes < field) OFC_TRY(s->repair_a.alloc(field));
-    if (rounds + smooth > 2 && s->repair_b.bytes < field) OFC_TRY(s->repair_b.alloc(field));
-    if (s->repair_filled.bytes < map) OFC_TRY(s->repair_filled.alloc(map));
+    OFC_TRY(reserve(s->repair_a, field));
+    if (rounds + smooth > 2) OFC_TRY(reserve(s->repair_b, field));
+    OFC_TRY(reserve(s->repair_filled, map));
     s->repair_on = true;
     s->repair_keep = keep;
     s->repair_radius = radius;
@@ -749,14 +636,13 @@ int ofc_stream_read_repair(ofc_stream_t *s, int64_t *counts_host, int max_pairs)
 {
     OFC_REQUIRE(s, "null pointer");
     OFC_REQUIRE(s->repair_on, "the stream has no repair (ofc_stream_set_repair)");
-    OFC_REQUIRE(s->pairs_submitted == 0 && s->slot[0].n_frames == 0 && s->slot[1].n_frames == 0,
-                "the stream holds frames or undelivered results: read the repair counts straight after a finish");
+    OFC_TRY(require_idle(s, "read the repair counts straight after a finish"));
     OFC_REQUIRE(max_pairs >= s->repair_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->repair_pairs);
     OFC_TRY(ensure_device(s->device));
     if (!s->repair_pairs) return OFC_OK;
     OFC_REQUIRE(counts_host, "null pointer");
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
-    OFC_HIP(hipMemcpy(counts_host, s->repair_counts.p, sizeof(int64_t) * REPAIR_NCOUNT * (size_t)s->repair_pairs, hipMemcpyDeviceToHost));
+    OFC_HIP(hipMemcpy(counts_host, s->repair_counts.buf.p, s->repair_counts.per * (size_t)s->repair_pairs, hipMemcpyDeviceToHost));
     return OFC_OK;
 }
 

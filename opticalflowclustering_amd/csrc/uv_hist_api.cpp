@@ -1,6 +1,7 @@
 // uv_hist_api.cpp -- C ABI of libofc.so, part 5: the histogram of flow vectors (uv_hist.hip) on device and host buffers,
 // and its measurement hook.  The streaming ingest's table is stream_api.cpp's.
 #include "color_common.h"
+#include "host_util.h"
 
 using namespace ofc;
 
@@ -53,20 +54,8 @@ int ofc_bench_uv_hist(int device, const float *flow_dev, int64_t n, int bins, fl
     OFC_TRY(t.alloc(table_bytes(bins)));
     OFC_HIP(hipMemset(t.p, 0, t.bytes));
     hipStream_t s = nullptr;
-    hipEvent_t e0, e1;
-    OFC_HIP(hipEventCreate(&e0));
-    OFC_HIP(hipEventCreate(&e1));
-    for (int w = 0; w < 2; w++) OFC_TRY(launch_uv_hist(flow_dev, n, bins, range, t.as<int64_t>(), s));
-    OFC_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; i++) OFC_TRY(launch_uv_hist(flow_dev, n, bins, range, t.as<int64_t>(), s));
-    OFC_HIP(hipEventRecord(e1, s));
-    OFC_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    OFC_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return OFC_OK;
+    auto launch = [&]() -> int { return launch_uv_hist(flow_dev, n, bins, range, t.as<int64_t>(), s); };
+    return time_launches(s, iters, launch, ms_per_launch);
 }
 
 }  // extern "C"

@@ -394,6 +394,32 @@ def test_stream_repair_equals_the_resident_route_and_can_be_removed(clip, batch)
     alone.close()
 
 
+def test_stream_photometric_stats_and_repair_counts_grow_past_their_first_allocation(clip):
+    """frames cycling through 4 images, 261 pushes at batch_pairs = 8: the 33rd batch takes both tables past their 256 pairs.
+    Pair t is (image t % 4, image (t + 1) % 4), so its rows equal those of pair t % 4: the reference's, from the pairwise
+    fields of the four cyclic pairs, not a second stream's"""
+    from opticalflowclustering_amd.flow import FlowEngine
+    from opticalflowclustering_amd import photometric
+    images = clip.frames[:4]
+    eng = FlowEngine(PW, PH, max_batch=1)
+    fields = np.stack([eng.calc(images[t], images[(t + 1) % 4]) for t in range(4)])
+    eng.close()
+    state, want_stats, _ = PC.reference(images[[0, 1, 2, 3, 0]], fields, *photometric.quantise(**STRICT))
+    want_counts = RC.model(fields, state)[2]                                      # repair=True: the model's defaults
+    for want in (want_stats, want_counts):
+        assert len({r.tobytes() for r in want}) == 4                              # the four pairs differ: a misplaced row shows
+    st = _stream(8, photometric=dict(STRICT), repair=True)
+    for t in range(261):
+        st.push(images[t % 4])
+    assert len(st.finish()) == 260
+    stats, counts = st.photometric_stats(), st.repair_stats()
+    st.close()
+    assert stats.shape == (260, 5) and counts.shape == (260, 3)
+    for t in range(260):
+        assert np.array_equal(stats[t], want_stats[t % 4]), t
+        assert np.array_equal(counts[t], want_counts[t % 4]), t
+
+
 def test_stream_set_repair_and_read_repair_refusals(clip):
     L = _L()
     lib = L.load()
