@@ -366,10 +366,13 @@ int launch_level_image(const uint8_t *src, float *dst, int nimg, int W0, int H0,
 //                   keeps an (8 + 2N)-row register window of its column that slides down 8 rows per chunk; the 8 new rows
 //                   are requested right after the barrier (lanes <-> x: coalesced), so their latency hides
 //                   under the horizontal pass.  The window yields the three f32 moments t0,t1,t2 of 8 rows with
-//                   the symmetric / antisymmetric tap pairing of the reference -> LDS [3][8][256].
+//                   the symmetric / antisymmetric tap pairing of the reference -> LDS, one float4 per pixel.
 //   horizontal pass wave <-> row, lane <-> 4 consecutive x: 4 + 2N ds_read_b128 (forced whole, see lds_read4),
-//                   accumulators as described in the loop, 5 float4 stores per lane (1 KiB/wave-instruction).
-// 24 KB LDS, 146 VGPRs -> 3 waves/SIMD.  Measured ceilings on MI355X for this traffic shape (tools/membench):
+//                   accumulators as described in the loop, 5 float4 stores per lane (1 KiB/wave-instruction),
+//                   staged through the moments row the wave has just read (no LDS beside the moments tile).
+// 39 936 B LDS; at poly_n 5 the f32 form takes 112 VGPRs and the u8 form 123, so four work-groups share a CU (4 waves
+// per SIMD); at poly_n 7 (132 / 143 VGPRs) three do.  DESIGN.md section 4 has the figures of every instantiation.
+// Measured ceilings on MI355X for this traffic shape (tools/membench):
 // 1 read : 5 write streams = 4.9 TB/s; this kernel's compute alone (stores off) = 5.9 TB/s-equivalent.
 // ------------------------------------------------------------------------------------------------
 // 16-byte LDS read that hipcc may not narrow: a plain float4 load whose tail elements are unused is split into
@@ -385,7 +388,10 @@ __device__ __forceinline__ float4 lds_read4(const float *p)
 
 constexpr int PE_TX = 240;
 constexpr int PE_CH = 8;
-constexpr int PE_PLANE = 66;    // float4 per (row, pixel & 3) plane of the moments tile: 64 + 2 -> bank-staggered
+// float4 per (row, pixel & 3) plane of the moments tile.  Two things set it: 4 * PE_PLANE = 24 mod 32 dwords staggers
+// the four planes over the banks (as 8 mod 32 does: 66, 74), and a row of four planes (4 992 B) holds a staged output
+// row (240 px x 5 coefficients = 4 800 B), which 66 and 74 do not.  8 rows x 4 992 B = 39 936 B per work-group.
+constexpr int PE_PLANE = 78;
 
 // N = poly_n, the half-width of the expansion window (cv2 documents 5 and 7; both are instantiated)
 template <int N>
@@ -399,12 +405,13 @@ struct PolyArgs {
 // U8IN: the pyramid's level 0 (3x3 [1/4 1/2 1/4] blur of the u8 frame, REFLECT_101, no decimation) is evaluated on the
 // fly from the frame instead of being read back as an f32 image: 1 B/px read instead of 4, and the level-0 image
 // kernel with its 5 B/px disappears.  Every intermediate value of that blur is a multiple of 1/16 below 256, exactly
-// representable in f32 whatever the evaluation order, so the result is bit-identical to k_level0 + this kernel.
+// representable in f32 whatever the evaluation order, so the result is bit-identical to k_level0 + this kernel; here the
+// sums are formed as integers (16 x the sample, <= 4 080) and scaled once.
 // F64H: the six horizontal sums exactly as the reference forms them (double accumulators; b1/b4 from double products, the
 // other four from float products) -- a study / fallback build (OFC_POLYEXP_F64=1): see DESIGN.md section 2.
 // N (last, so that the rocprof names of the poly_n=5 forms keep their prefix) is the window half-width: the strip needs
 // VW = 240 + 2N columns (250 / 254 <= 256 threads), the horizontal pass 4 + 2N moments per lane, whose highest LDS index
-// lane + (3 + 2N) / 4 = 63 at N = 7 stays inside the 66-float4 plane.
+// lane + (3 + 2N) / 4 = 63 at N = 7 stays inside the 78-float4 plane.
 template <int TAG, bool U8IN, bool F64H = false, int N = 5>
 __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv, float *__restrict__ R,
                                                  PolyArgs<N> p)
@@ -415,10 +422,12 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
     // vertical moments of the chunk, one float4 (t0, t1, t2, t1) per pixel: the horizontal pass consumes them as the
     // register pairs (t0,t1) and (t2,t1), which is what lets it run on packed-f32 instructions.  Pixel p of the strip
     // lives at [p & 3][p >> 2]: lane l of the horizontal pass reads pixels 4l+j, so for a fixed j the 64 lanes touch 64
-    // consecutive float4 of one plane (conflict-free ds_read_b128); planes are 66 float4 apart (264 dwords = 8 mod 32
+    // consecutive float4 of one plane (conflict-free ds_read_b128); planes are 78 float4 apart (312 dwords = 24 mod 32
     // banks) so that the vertical pass's writes, lane <-> pixel, spread over the banks as well.
+    // Row rr is read by one wave only (rr = wave, wave + 4), whole, before that wave's first use of it; from then until
+    // the next chunk's vertical pass (behind a work-group barrier) it is dead, and the wave stages its output row in it.
+    static_assert(4 * PE_PLANE * 4 >= PE_TX * 5, "a moments row must hold a staged output row");
     __shared__ __align__(16) float4 t4[PE_CH][4][PE_PLANE];
-    __shared__ __align__(16) float stage[4][PE_TX * 5 + 16];   // per-wave output row (240 px x 5 coefficients)
     typedef float v2f __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = p.W, H = p.H;
@@ -439,11 +448,15 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
     const int sh0 = U8IN ? 8 * (reflect101(xc - 1, W) - base) : 0, sh1 = U8IN ? 8 * (xc - base) : 0,
               sh2 = U8IN ? 8 * (reflect101(xc + 1, W) - base) : 0;
     auto hword = [&](int r) -> uint32_t { return *reinterpret_cast<const u32u *>(img8 + (size_t)r * W + base); };
-    auto hval = [&](uint32_t w) -> float {          // row-blurred sample (exact: a multiple of 1/4)
-        return 0.25f * (float)((w >> sh0) & 255u) + 0.5f * (float)((w >> sh1) & 255u) + 0.25f * (float)((w >> sh2) & 255u);
-    };
+    // The blur stays in integers until its last step: the row sum b(x-1) + 2 b(x) + b(x+1) <= 1 020 is one byte dot
+    // product against a per-thread weight word (1, 2, 1 on the three selected bytes; weights add where reflection makes
+    // two taps one byte), the column sum h(y-1) + 2 h(y) + h(y+1) <= 4 080 a shift-add and an add, and one conversion
+    // and one multiply by 1/16 give the level-0 sample: the value the f32 taps give, every partial sum of which is exact.
+    const uint32_t hwts = U8IN ? (1u << sh0) + (2u << sh1) + (1u << sh2) : 0u;
+    auto hsum = [&](uint32_t w) -> uint32_t { return __builtin_amdgcn_udot4(w, hwts, 0u, false); };   // 4 x row-blurred sample
+    auto i0_of = [&](uint32_t h0, uint32_t h1, uint32_t h2) -> float { return 0.0625f * (float)(h0 + 2u * h1 + h2); };
     auto i0_any = [&](int r) -> float {             // level-0 image at (valid) row r, any position: 3 row loads
-        return 0.25f * hval(hword(reflect101(r - 1, H))) + 0.5f * hval(hword(r)) + 0.25f * hval(hword(reflect101(r + 1, H)));
+        return i0_of(hsum(hword(reflect101(r - 1, H))), hsum(hword(r)), hsum(hword(reflect101(r + 1, H))));
     };
     // strips whose rows (incl. the +-1 blur rows) need neither clamping nor reflection share the row-blurred samples
     // between consecutive level-0 rows: 10 + 2N + 8 per chunk dword loads per thread, the count of the f32 path
@@ -453,17 +466,17 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
     // rows are requested right after the barrier so that their HBM latency hides under the horizontal pass
     float s[8 + 2 * N], nxt[8];
     uint32_t nxtw[8];
-    float hk0 = 0.f, hk1 = 0.f;                         // U8IN interior: row-blurred samples of window rows 8+2N, 9+2N
+    uint32_t hk0 = 0u, hk1 = 0u;                        // U8IN interior: row sums of window rows 8+2N, 9+2N
     if (!U8IN) {
 #pragma unroll
         for (int j = 0; j < 8 + 2 * N; j++)
             s[j] = img[(size_t)min(max(y_begin - N + j, 0), H - 1) * W + xc];
     } else if (interior) {
-        float hv[8 + 2 * N + 2];
+        uint32_t hv[8 + 2 * N + 2];
 #pragma unroll
-        for (int j = 0; j < 8 + 2 * N + 2; j++) hv[j] = hval(hword(y_begin - N - 1 + j));
+        for (int j = 0; j < 8 + 2 * N + 2; j++) hv[j] = hsum(hword(y_begin - N - 1 + j));
 #pragma unroll
-        for (int j = 0; j < 8 + 2 * N; j++) s[j] = 0.25f * hv[j] + 0.5f * hv[j + 1] + 0.25f * hv[j + 2];
+        for (int j = 0; j < 8 + 2 * N; j++) s[j] = i0_of(hv[j], hv[j + 1], hv[j + 2]);
         hk0 = hv[8 + 2 * N];
         hk1 = hv[8 + 2 * N + 1];
     } else {
@@ -509,6 +522,7 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
             const int y = yc + rr;
             if (y >= y_end) break;
             const int xo = x0 + 4 * lane;
+            float *const stage = reinterpret_cast<float *>(&t4[rr][0][0]);   // this wave's, once its moments are read
             if (lane < PE_TX / 4 && xo < W) {
                 v2f A[4 + 2 * N], Q[4 + 2 * N];   // (t0, t1) and (t2, t1) of strip pixels 4*lane .. 4*lane + 3 + 2N
 #pragma unroll
@@ -581,10 +595,13 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
                 // R is pixel-interleaved ([y][x][5], as OpenCV keeps it) so that the consumer's bilinear taps are two
                 // 40-byte runs instead of 20 scattered dwords.  A lane's 4 px x 5 coefficients are 80 contiguous bytes;
                 // storing them directly would make every wave-instruction write 16 B out of each 80 (measured: 5x
-                // slower).  They cross a per-wave LDS row instead (conflict-free at the 80-B lane stride) and leave as
-                // five fully contiguous 1-KiB wave stores.
+                // slower).  They cross the wave's own moments row instead (conflict-free at the 80-B lane stride) and
+                // leave as five fully contiguous 1-KiB wave stores.  Every lane's moments are in registers by now (the
+                // coefficients above depend on all of them); the wave barrier keeps the compiler from moving a staging
+                // write of one lane above a moments read of another.
                 if (vec_ok) {
-                    float *sg = &stage[wave][20 * lane];
+                    __builtin_amdgcn_wave_barrier();
+                    float *sg = stage + 20 * lane;
                     *reinterpret_cast<float4 *>(sg) = make_float4(r0[0], r1[0], r2[0], r3[0]);
                     *reinterpret_cast<float4 *>(sg + 4) = make_float4(r4[0], r0[1], r1[1], r2[1]);
                     *reinterpret_cast<float4 *>(sg + 8) = make_float4(r3[1], r4[1], r0[2], r1[2]);
@@ -609,7 +626,7 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
                 for (int j = 0; j < 5; j++) {
                     const int idx = lane + 64 * j;
                     if (idx < nf4) {
-                        const float4 v = lds_read4(&stage[wave][4 * idx]);
+                        const float4 v = lds_read4(stage + 4 * idx);
                         __builtin_nontemporal_store((v4f){v.x, v.y, v.z, v.w}, orow + idx);
                     }
                 }
@@ -620,13 +637,13 @@ __global__ __launch_bounds__(256, 3) void k_polyexp(const void *__restrict__ Iv,
 #pragma unroll
         for (int j = 0; j < 2 * N; j++) s[j] = s[j + 8];
         if (U8IN && interior) {
-            float hn[10];
+            uint32_t hn[10];
             hn[0] = hk0;
             hn[1] = hk1;
 #pragma unroll
-            for (int j = 0; j < 8; j++) hn[2 + j] = hval(nxtw[j]);
+            for (int j = 0; j < 8; j++) hn[2 + j] = hsum(nxtw[j]);
 #pragma unroll
-            for (int j = 0; j < 8; j++) s[2 * N + j] = 0.25f * hn[j] + 0.5f * hn[j + 1] + 0.25f * hn[j + 2];
+            for (int j = 0; j < 8; j++) s[2 * N + j] = i0_of(hn[j], hn[j + 1], hn[j + 2]);
             hk0 = hn[8];
             hk1 = hn[9];
         } else {
