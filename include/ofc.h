@@ -117,6 +117,11 @@ int ofc_flow_sync(ofc_flow_t *f);
  * set in the environment when the engine was created.  Everything a call issues is ordered before whatever follows it on
  * the engine's stream: callers synchronise as before. */
 int ofc_flow_front_overlap(const ofc_flow_t *f, int *on);
+/* *on = 1 when the engine writes the level images of all its coarse levels with one launch per batch (k_pyramid_dec: one
+ * march over the u8 frames) instead of one launch per level: with the overlap above on, at most three coarse levels, every one
+ * an exact decimation by 2, 4, 8 (pyr_scale 0.5 on frames whose sides divide), and OFC_PYRAMID_FUSED=0 not set in the
+ * environment when the engine was created.  The images are the same bits either way. */
+int ofc_flow_pyramid_fused(const ofc_flow_t *f, int *on);
 
 /* streaming form of ComputeOpticalFLow (computeOpticalFlowModule.py:6-36): keeps the previous
  * frame; the first push returns OFC_ENOTREADY and writes nothing.
@@ -140,6 +145,18 @@ int ofc_flow_last_vis_dev(ofc_flow_t *f, const uint8_t **vis_dev);
 /* u8 frame -> f32 pyramid image of level k (GaussianBlur at full res + INTER_LINEAR resize) */
 int ofc_level_image(int device, const uint8_t *gray, int W, int H, const ofc_fb_params *p, int k,
                     float *out, int *w_out, int *h_out);
+/* u8 frames [n][H0][W0] -> the f32 images of pyramid levels 1..levels (1..3) at the default pyr_scale 0.5, [n][h][w] each.
+ * fused != 0: the leading levels that are exact decimations come from one k_pyramid_dec launch (*fused_levels says how many)
+ * and the others from the per-level kernels; fused == 0: every level from the per-level kernels, as ofc_level_image.  The
+ * pyramid's minimum level size is not applied: the hook reaches small levels the engine would drop. */
+int ofc_pyramid_dec(int device, const uint8_t *frames, int n, int W0, int H0, int levels, int fused,
+                    float *out1, float *out2, float *out3, int *fused_levels);
+/* out = {bands of 256 input columns, 8-row steps per frame, steps per strip, strips} of a k_pyramid_dec launch over n frames.
+ * Host only. */
+int ofc_pyramid_dec_geometry(int W0, int H0, int n, int out[4]);
+/* bench hook: ms per batch of the level images 1..levels of n_images resident W x H frames, timed with HIP events: fused 1 =
+ * one k_pyramid_dec launch (OFC_EUNSUPPORTED where the levels are not all exact decimations), 0 = the per-level launches */
+int ofc_bench_pyramid_dec(int device, int W, int H, int n_images, int levels, int fused, int iters, float *ms_per_batch);
 /* FarnebackPolyExp: f32 HxW -> f32 HxWx5 {y-lin, x-lin, y^2, x^2, xy}; n (poly_n) 5 or 7, else OFC_EUNSUPPORTED */
 int ofc_polyexp(int device, const float *img, int W, int H, int n, double sigma, float *R5);
 /* the same for pyramid level 0 straight from the u8 frame (level-0 blur fused in; what ofc_flow_* runs at level 0):

@@ -65,6 +65,7 @@ _PROTOS = {
     "ofc_flow_calc_frames_dev_stats": ([_vp, _vp, _i, _vp, _vp], _i),
     "ofc_flow_sync": ([_vp], _i),
     "ofc_flow_front_overlap": ([_vp, _ip], _i),
+    "ofc_flow_pyramid_fused": ([_vp, _ip], _i),
     "ofc_flow_push_gray": ([_vp, _vp, _vp], _i),
     "ofc_flow_push_bgr": ([_vp, _vp, _vp, C.POINTER(_f), _vp], _i),
     "ofc_flow_last_vis_dev": ([_vp, C.POINTER(_vp)], _i),
@@ -76,6 +77,9 @@ _PROTOS = {
     "ofc_flow_resize": ([_i, _vp, _i, _i, _i, _i, _f, _vp], _i),
     "ofc_flow_iterate": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "ofc_flow_launch_geometry": ([_i, _i, _i, _i, _ip], _i),
+    "ofc_pyramid_dec": ([_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ip], _i),
+    "ofc_pyramid_dec_geometry": ([_i, _i, _i, _ip], _i),
+    "ofc_bench_pyramid_dec": ([_i, _i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_bench_flow_iters": ([_i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_bench_polyexp": ([_i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_bgr2gray": ([_i, _vp, _i, _i, _vp], _i),

@@ -358,6 +358,323 @@ int launch_level_image(const uint8_t *src, float *dst, int nimg, int W0, int H0,
 }
 
 // ------------------------------------------------------------------------------------------------
+// K2 fused: the exact-decimation levels 1..L (L <= 3: 2x / 3 taps, 4x / 9 taps, 8x / 19 taps) of a batch from ONE march
+// over the u8 frames.  Every value is computed by k_level_dec's statements in k_level_dec's order, contraction off, so the
+// images are the same bits; only the data movement and which values share a packed instruction differ.
+//
+// Work-group = 256 threads, one band of 256 input columns (128 + 64 + 32 output columns) of one strip of one frame,
+// marched in steps of 8 input rows.  Step t:
+//   stage     the bytes of rows 8t+7 .. 8t+14 (REFLECT_101 in y and, at the frame's sides, in x), columns x0-8 .. x0+263,
+//             were requested one step ahead as 544 coalesced dwords and go to LDS: 2 176 B
+//   barrier
+//   request   the next step's rows
+//   row pass  of the 8 new rows at all levels -> one LDS ring per level, float2 = the two x positions of an output column.
+//             An item is one window in TWO rows, four apart (packed f32, one lane per row): level 3, 32 columns x 4 row
+//             pairs, on waves 0-1; level 2, 64 x 4, two items a thread on waves 2-3 (as many instructions as a level 3 item);
+//             then level 1, two adjacent columns x 4 row pairs, an item for every thread
+//   barrier
+//   column pass of the output rows whose windows end in row 8t+14: level 1 rows 4t+3 .. 4t+6 (waves 0-1, a thread owns a
+//             column and reads its ten ring rows once), level 2 rows 2t+1, 2t+2 (wave 2), level 3 row t (half of wave 3)
+// A ring holds whole steps: 16 rows at levels 1 and 2 (windows of 10 and 14 rows behind row 8t+14), 24 at level 3 (20 rows):
+// 16 + 8 + 6 KB.  The slot of every ring access is a compile-time constant: the step body is instantiated for the six
+// values of t mod 6.  No input row is row-filtered twice inside a strip; a strip warms up with the row passes of two
+// steps (level 3) / one step (levels 1, 2).  Rows above the frame are the steps -2 and -1 of the first strip, which row-filters
+// both at all levels and writes level 1 rows 0 .. 2 and level 2 row 0 in step -1.
+// ------------------------------------------------------------------------------------------------
+struct PyrDecArgs {
+    int W0, H0;
+    int steps, sps;              // 8-row steps per frame; steps per strip
+    int w[3], h[3];
+    float k1[2], k2[5], k3[10];  // taps 0..R of each level's kernel; tap q > R is tap 2R-q (gaussian_kernel computes both from the
+                                 // same x*x: the same float), which halves the scalar registers the taps hold
+};
+
+constexpr int PD_BAND = 256;     // input columns per work-group
+constexpr int PD_SW = 68;        // staged dwords per row: bytes x0-8 .. x0+263
+
+typedef float pd_v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ pd_v2f pd_ld2(const float2 *p) { const float2 v = *p; return pd_v2f{v.x, v.y}; }
+
+// the two row sums of k_level_dec, a0 = sum k[q] b[q] and a1 = sum k[q] b[q+1], each left to right, for TWO input rows at once:
+// b[q] = (byte q of the window in the first row, the same in the second), so that one packed operation serves both rows,
+// the tap is one scalar register and no operand has to be moved into place
+template <int R>
+__device__ __forceinline__ void pd_row_sums(const pd_v2f *b, const float *kh, pd_v2f &a0, pd_v2f &a1)
+{
+#pragma clang fp contract(off)
+    a0 = kh[0] * b[0];
+    a1 = kh[0] * b[1];
+#pragma unroll
+    for (int q = 1; q <= 2 * R; q++) {
+        const float k = kh[q <= R ? q : 2 * R - q];
+        a0 += k * b[q];
+        a1 += k * b[q + 1];
+    }
+}
+
+// k_level_dec's column pass on a window of 2R+2 ring rows (centre first, then the symmetric pairs; the two mixes); the two
+// x positions of a ring entry are the two lanes of the packed operations
+template <int R>
+__device__ __forceinline__ float pd_col(const pd_v2f *win, const float *kh)
+{
+#pragma clang fp contract(off)
+    float hy[2];
+#pragma unroll
+    for (int yt = 0; yt < 2; yt++) {
+        pd_v2f v = kh[R] * win[R + yt];
+#pragma unroll
+        for (int m = 1; m <= R; m++) v += kh[R - m] * (win[R + yt - m] + win[R + yt + m]);
+        hy[yt] = v.x * 0.5f + v.y * 0.5f;
+    }
+    return hy[0] * 0.5f + hy[1] * 0.5f;
+}
+
+template <int L>
+__global__ __launch_bounds__(256, 4) void k_pyramid_dec(const uint8_t *__restrict__ src, float *__restrict__ dst1,
+                                                     float *__restrict__ dst2, float *__restrict__ dst3, PyrDecArgs p)
+{
+#pragma clang fp contract(off)
+    __shared__ __align__(16) uint32_t stg[8][PD_SW];
+    __shared__ __align__(16) float2 ring1[16][128];
+    __shared__ float2 ring2[L >= 2 ? 16 : 1][64];
+    __shared__ float2 ring3[L >= 3 ? 24 : 1][32];
+    const int tid = threadIdx.x, W0 = p.W0, H0 = p.H0;
+    const int band = blockIdx.x, x0 = band * PD_BAND;
+    const int t0 = blockIdx.y * p.sps, t1 = min(p.steps, t0 + p.sps);
+    const bool first = t0 == 0, last = t1 == p.steps;
+    const uint8_t *img = src + (size_t)blockIdx.z * W0 * H0;
+    // output rows of this strip: step t writes level 1 rows 4t+3 .. 4t+6, level 2 rows 2t+1, 2t+2, level 3 row t, and the
+    // first strip also what step -1 writes
+    const int lo1 = first ? 0 : 4 * t0 + 3, hi1 = last ? p.h[0] : min(p.h[0], 4 * t1 + 3);
+    const int lo2 = first ? 0 : 2 * t0 + 1, hi2 = last ? p.h[1] : min(p.h[1], 2 * t1 + 1);
+    const int hi3 = min(p.h[2], t1);
+    float *out1 = dst1 + (size_t)blockIdx.z * p.w[0] * p.h[0];
+    float *out2 = L >= 2 ? dst2 + (size_t)blockIdx.z * p.w[1] * p.h[1] : nullptr;
+    float *out3 = L >= 3 ? dst3 + (size_t)blockIdx.z * p.w[2] * p.h[2] : nullptr;
+
+    // staging: slot = tid + 256 n of the 8 x 68 dwords; its row and column stay, the frame row moves with the step
+    int srow[3], scol[3], smode[3];           // mode 0: one aligned dword; 1: four reflected bytes; 2: beyond what any window reads
+#pragma unroll
+    for (int n = 0; n < 3; n++) {
+        const int s = min(tid + 256 * n, 8 * PD_SW - 1);
+        srow[n] = s / PD_SW;
+        const int c = s - srow[n] * PD_SW;
+        scol[n] = x0 - 8 + 4 * c;
+        smode[n] = (scol[n] >= 0 && scol[n] + 4 <= W0) ? 0 : (scol[n] < W0 + 8 ? 1 : 2);
+    }
+    const bool third = tid < 8 * PD_SW - 512;
+    uint32_t d[3];
+    auto fetch = [&](int t) {
+#pragma unroll
+        for (int n = 0; n < 3; n++) {
+            if (n == 2 && !third) break;
+            const int v = 8 * t + 7 + srow[n];
+            int y = v < 0 ? -v : (v >= H0 ? 2 * (H0 - 1) - v : v);
+            y = min(max(y, 0), H0 - 1);       // (rows no window of this frame reads may lie further out than one reflection)
+            const uint8_t *row = img + (size_t)y * W0;
+            if (smode[n] == 0) {
+                d[n] = *reinterpret_cast<const uint32_t *>(row + scol[n]);
+            } else if (smode[n] == 1) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int e = 0; e < 4; e++) {     // |overshoot| <= 8 < W0 (level_image_plan)
+                    const int x = scol[n] + e, xr = x < 0 ? -x : (x >= W0 ? 2 * (W0 - 1) - x : x);
+                    w |= (uint32_t)row[min(max(xr, 0), W0 - 1)] << (8 * e);
+                }
+                d[n] = w;
+            } else {
+                d[n] = 0;
+            }
+        }
+    };
+
+    // row-pass items: a thread takes the same window in two of the step's rows, r and r + 4 (r + 2 and r + 6)
+    auto step = [&](auto phc, int t, bool rows12, bool col12, bool col3) {
+        constexpr int PH = decltype(phc)::value, P2 = PH % 2, P3 = PH % 3;
+        if (tid < 128) {
+            if constexpr (L >= 3) {       // level 3: 32 columns x 4 row pairs
+                const int j = tid & 31, r = tid >> 5;
+                uint32_t wd[2][6];
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    const uint2 *w2 = reinterpret_cast<const uint2 *>(&stg[r + 4 * i][2 * j]);
+                    const uint2 wa = w2[0], wb = w2[1], wc = w2[2];
+                    wd[i][0] = wa.x; wd[i][1] = wa.y; wd[i][2] = wb.x; wd[i][3] = wb.y; wd[i][4] = wc.x; wd[i][5] = wc.y;
+                }
+                pd_v2f b[20], a0, a1;
+#pragma unroll
+                for (int q = 0; q < 20; q++)
+                    b[q] = pd_v2f{ubyte_of(wd[0][(2 + q) >> 2], (2 + q) & 3), ubyte_of(wd[1][(2 + q) >> 2], (2 + q) & 3)};
+                pd_row_sums<9>(b, p.k3, a0, a1);
+                ring3[P3 * 8 + r][j] = make_float2(a0.x, a1.x);
+                ring3[P3 * 8 + r + 4][j] = make_float2(a0.y, a1.y);
+            }
+        } else if (rows12) {
+            if constexpr (L >= 2) {       // level 2: 64 columns x 2 x 2 row pairs
+                const int j = tid & 63, r = (tid >> 6) & 1;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    uint32_t wd[2][3];
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const uint32_t *w1 = &stg[r + 2 * h + 4 * i][j + 1];
+                        wd[i][0] = w1[0]; wd[i][1] = w1[1]; wd[i][2] = w1[2];
+                    }
+                    pd_v2f b[10], a0, a1;
+#pragma unroll
+                    for (int q = 0; q < 10; q++)
+                        b[q] = pd_v2f{ubyte_of(wd[0][(1 + q) >> 2], (1 + q) & 3), ubyte_of(wd[1][(1 + q) >> 2], (1 + q) & 3)};
+                    pd_row_sums<4>(b, p.k2, a0, a1);
+                    ring2[P2 * 8 + r + 2 * h][j] = make_float2(a0.x, a1.x);
+                    ring2[P2 * 8 + r + 2 * h + 4][j] = make_float2(a0.y, a1.y);
+                }
+            }
+        }
+        if (rows12) {                     // level 1: 64 pairs of columns x 4 row pairs
+            const int c = tid & 63, r = tid >> 6;
+            uint32_t wd[2][3];
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                const uint32_t *w1 = &stg[r + 4 * i][c + 1];
+                wd[i][0] = w1[0]; wd[i][1] = w1[1]; wd[i][2] = w1[2];
+            }
+            pd_v2f b[6], a0[2], a1[2];
+#pragma unroll
+            for (int q = 0; q < 6; q++)
+                b[q] = pd_v2f{ubyte_of(wd[0][(3 + q) >> 2], (3 + q) & 3), ubyte_of(wd[1][(3 + q) >> 2], (3 + q) & 3)};
+#pragma unroll
+            for (int e = 0; e < 2; e++) pd_row_sums<1>(b + 2 * e, p.k1, a0[e], a1[e]);
+            *reinterpret_cast<float4 *>(&ring1[P2 * 8 + r][2 * c]) = make_float4(a0[0].x, a1[0].x, a0[1].x, a1[1].x);
+            *reinterpret_cast<float4 *>(&ring1[P2 * 8 + r + 4][2 * c]) = make_float4(a0[0].y, a1[0].y, a0[1].y, a1[1].y);
+        }
+        __syncthreads();
+        if (tid < 128) {
+            const int ox = 128 * band + tid;
+            if (col12 && ox < p.w[0]) {
+                pd_v2f win[10];               // rows 8t+5 .. 8t+14
+#pragma unroll
+                for (int q = 0; q < 10; q++) win[q] = pd_ld2(&ring1[(P2 * 8 + q - 2 + 16) % 16][tid]);
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+                    const int oy = 4 * t + 3 + a;
+                    const float v = pd_col<1>(win + 2 * a, p.k1);
+                    if (oy >= lo1 && oy < hi1) out1[(size_t)oy * p.w[0] + ox] = v;
+                }
+            }
+        } else if (tid < 192) {
+            if constexpr (L >= 2) {
+                const int j = tid - 128, ox = 64 * band + j;
+                if (col12 && ox < p.w[1]) {
+                    pd_v2f win[14];           // rows 8t+1 .. 8t+14
+#pragma unroll
+                    for (int q = 0; q < 14; q++) win[q] = pd_ld2(&ring2[(P2 * 8 + q - 6 + 16) % 16][j]);
+#pragma unroll
+                    for (int a = 0; a < 2; a++) {
+                        const int oy = 2 * t + 1 + a;
+                        const float v = pd_col<4>(win + 4 * a, p.k2);
+                        if (oy >= lo2 && oy < hi2) out2[(size_t)oy * p.w[1] + ox] = v;
+                    }
+                }
+            }
+        } else if (tid < 224) {
+            if constexpr (L >= 3) {
+                const int j = tid - 192, ox = 32 * band + j;
+                if (col3 && t < hi3 && ox < p.w[2]) {
+                    pd_v2f win[20];           // rows 8t-6 .. 8t+13
+#pragma unroll
+                    for (int q = 0; q < 20; q++) win[q] = pd_ld2(&ring3[(P3 * 8 + q - 13 + 24) % 24][j]);
+                    out3[(size_t)t * p.w[2] + ox] = pd_col<9>(win, p.k3);
+                }
+            }
+        }
+    };
+
+    // the first warm-up step: two ahead at level 3, one at levels 1 and 2; level 2's row 0 (written by step -1) reads rows
+    // -3 and -2 of step -2
+    const int tb = (L >= 3 || (L >= 2 && first)) ? t0 - 2 : t0 - 1;
+    int ph = (tb + 6) % 6;
+    fetch(tb);
+    for (int t = tb; t < t1; t++) {
+#pragma unroll
+        for (int n = 0; n < 3; n++)
+            if (n < 2 || third) stg[srow[n]][(scol[n] - x0 + 8) >> 2] = d[n];
+        __syncthreads();
+        if (t + 1 < t1) fetch(t + 1);
+        const bool rows12 = t >= t0 - 1 || t < 0, col12 = t >= t0 || t == -1, col3 = t >= t0;
+        switch (ph) {
+        case 0: step(std::integral_constant<int, 0>{}, t, rows12, col12, col3); break;
+        case 1: step(std::integral_constant<int, 1>{}, t, rows12, col12, col3); break;
+        case 2: step(std::integral_constant<int, 2>{}, t, rows12, col12, col3); break;
+        case 3: step(std::integral_constant<int, 3>{}, t, rows12, col12, col3); break;
+        case 4: step(std::integral_constant<int, 4>{}, t, rows12, col12, col3); break;
+        default: step(std::integral_constant<int, 5>{}, t, rows12, col12, col3); break;
+        }
+        ph = ph == 5 ? 0 : ph + 1;
+    }
+}
+
+// The launch geometry of k_pyramid_dec: bands of 256 input columns, 8-row steps, and strips of whole steps so that a batch
+// gives about four work-groups to each of the 256 CUs (61 frames of 1080p: 8 bands x 2 strips = 976); a strip is at least
+// four steps, its warm-up being two.
+void pyramid_dec_plan(int W0, int H0, int nimg, int &bands, int &steps, int &sps, int &strips)
+{
+    bands = cdiv(W0, PD_BAND);
+    steps = cdiv(H0, 8);
+    const int64_t nb = std::max<int64_t>(1, (int64_t)nimg * bands);
+    const int want = (int)std::max<int64_t>(1, (1024 + nb / 2) / nb);
+    sps = std::max(4, cdiv(steps, want));
+    strips = cdiv(steps, sps);
+}
+
+// how many of the coarse levels 1..levels (geom[1..]) one k_pyramid_dec launch writes: the leading ones, three at the
+// most, that take k_level_dec's paths 2, 4, 8 in that order
+int pyramid_dec_levels(int W0, int H0, const LevelGeom *geom, int levels, bool src_aligned)
+{
+    static const int want[3] = {2, 4, 8};
+    int n = 0;
+    for (int k = 1; k <= std::min(levels, 3); k++) {
+        LevelArgs a;
+        int path = 1;
+        size_t lds = 0;
+        if (level_image_plan(W0, H0, geom[k], src_aligned, a, path, lds) != OFC_OK || path != want[k - 1]) break;
+        n = k;
+    }
+    return n;
+}
+
+// levels 1..L (L = pyramid_dec_levels(...) >= 1, the caller's check) of nimg frames into dst[0..L-1]
+int launch_pyramid_dec(const uint8_t *src, float *const *dst, int nimg, int W0, int H0, const LevelGeom *geom, int L,
+                       hipStream_t s)
+{
+    OFC_REQUIRE(L >= 1 && L <= 3 && pyramid_dec_levels(W0, H0, geom, L, ((uintptr_t)src % 4) == 0) == L,
+                "k_pyramid_dec: levels 1..%d of %d x %d are not all exact decimations", L, W0, H0);
+    PyrDecArgs p;
+    memset(&p, 0, sizeof(p));
+    p.W0 = W0; p.H0 = H0;
+    int bands, strips;
+    pyramid_dec_plan(W0, H0, nimg, bands, p.steps, p.sps, strips);
+    for (int k = 1; k <= L; k++) {
+        LevelArgs a;
+        int path = 1;
+        size_t lds = 0;
+        OFC_TRY(level_image_plan(W0, H0, geom[k], true, a, path, lds));
+        p.w[k - 1] = geom[k].w; p.h[k - 1] = geom[k].h;
+        for (int q = 0; q < a.r; q++)
+            OFC_REQUIRE(a.kern[q] == a.kern[2 * a.r - q], "k_pyramid_dec: level %d's kernel is not symmetric", k);
+        memcpy(k == 1 ? p.k1 : k == 2 ? p.k2 : p.k3, a.kern, sizeof(float) * (a.r + 1));
+    }
+    const dim3 grid(bands, strips, nimg);
+    float *d1 = dst[0], *d2 = L >= 2 ? dst[1] : nullptr, *d3 = L >= 3 ? dst[2] : nullptr;
+    switch (L) {
+    case 1: hipLaunchKernelGGL(k_pyramid_dec<1>, grid, dim3(256), 0, s, src, d1, d2, d3, p); break;
+    case 2: hipLaunchKernelGGL(k_pyramid_dec<2>, grid, dim3(256), 0, s, src, d1, d2, d3, p); break;
+    default: hipLaunchKernelGGL(k_pyramid_dec<3>, grid, dim3(256), 0, s, src, d1, d2, d3, p);
+    }
+    OFC_HIP(hipGetLastError());
+    return OFC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // K3  polynomial expansion (the north-star kernel).  24 B/px algorithmic: 4 read + 20 written.
 //
 // Work-group = 256 threads = 4 waves, output strip 240 columns x rows_per_block rows, walked in chunks

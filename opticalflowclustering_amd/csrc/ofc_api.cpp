@@ -235,6 +235,9 @@ struct ofc_flow {
     hipEvent_t fork = nullptr;
     std::vector<hipEvent_t> ready;  // [0..levels], [0] unused (null)
     std::vector<size_t> offI, offR; // [0..levels]
+    // With the overlap on, the level images of all coarse levels come from one k_pyramid_dec launch on the side stream when
+    // every one of them is an exact decimation (at most three: 2x, 4x, 8x); OFC_PYRAMID_FUSED=0 keeps the per-level launches
+    bool pyramid_fused = false;
     bool fused = true;              // update-matrices fused into the box/solve kernel (winsize <= 15); otherwise the staged
                                     // kernels: k_box_solve<8> at 17, k_box_solve_wide from 19 on
     bool fuse_level0 = true;        // polyexp of level 0 reads the u8 frames (no f32 level-0 image)
@@ -291,8 +294,19 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
         // iterations want them in), and the level-0 front end beside them on the main stream.
         OFC_HIP(hipEventRecord(f->fork, s));
         OFC_HIP(hipStreamWaitEvent(f->side, f->fork, 0));
+        const bool one_launch = f->pyramid_fused && ((uintptr_t)frames_dev % 4) == 0;
+        if (one_launch) {
+            float *lv[3] = {nullptr, nullptr, nullptr};
+            for (int k = 1; k <= f->levels; k++) lv[k - 1] = f->I.as<float>() + f->offI[k];
+            OFC_TRY(launch_pyramid_dec(frames_dev, lv, n_frames, W, H, f->geom.data(), f->levels, f->side));
+        }
         for (int k = f->levels; k >= 1; k--) {
-            OFC_TRY(front_end(k, f->side));
+            if (one_launch) {
+                const LevelGeom &g = f->geom[k];
+                OFC_TRY(launch_polyexp(f->I.as<float>() + f->offI[k], f->R.as<float>() + f->offR[k], n_frames, g.w, g.h, f->pc, 0, f->side));
+            } else {
+                OFC_TRY(front_end(k, f->side));
+            }
             OFC_HIP(hipEventRecord(f->ready[k], f->side));
         }
         OFC_TRY(front_end(0, s));
@@ -503,6 +517,11 @@ int ofc_flow_create(int device, int W, int H, const ofc_fb_params *p, int max_ba
             nI = sI; nR = sR;
         }
     }
+    {
+        const char *ep = getenv("OFC_PYRAMID_FUSED");
+        f->pyramid_fused = !(ep && ep[0] == '0') && f->front_overlap && f->levels <= 3 &&
+                           pyramid_dec_levels(W, H, f->geom.data(), f->levels, true) == f->levels;
+    }
     if (f->front_overlap) {
         OFC_HIP(hipStreamCreateWithFlags(&f->side, hipStreamNonBlocking));
         OFC_HIP(hipEventCreateWithFlags(&f->fork, hipEventDisableTiming));
@@ -577,6 +596,13 @@ int ofc_flow_front_overlap(const ofc_flow_t *f, int *on)
 {
     OFC_REQUIRE(f && on, "null pointer");
     *on = f->front_overlap ? 1 : 0;
+    return OFC_OK;
+}
+
+int ofc_flow_pyramid_fused(const ofc_flow_t *f, int *on)
+{
+    OFC_REQUIRE(f && on, "null pointer");
+    *on = f->pyramid_fused ? 1 : 0;
     return OFC_OK;
 }
 
@@ -694,6 +720,46 @@ int ofc_level_image(int device, const uint8_t *gray, int W, int H, const ofc_fb_
     OFC_HIP(hipMemcpy(out, dst.p, sizeof(float) * g.w * g.h, hipMemcpyDeviceToHost));
     if (w_out) *w_out = g.w;
     if (h_out) *h_out = g.h;
+    return OFC_OK;
+}
+
+int ofc_pyramid_dec(int device, const uint8_t *frames, int n, int W0, int H0, int levels, int fused,
+                    float *out1, float *out2, float *out3, int *fused_levels)
+{
+    OFC_REQUIRE(frames && out1 && (levels < 2 || out2) && (levels < 3 || out3), "null pointer");
+    OFC_REQUIRE(n >= 1 && levels >= 1 && levels <= 3, "n >= 1 frames and 1..3 levels");
+    ofc_fb_params prm;
+    ofc_fb_default_params(&prm);
+    prm.levels = levels;
+    OFC_TRY(check_params(prm, W0, H0));
+    std::vector<LevelGeom> geom;
+    for (int k = 0; k <= levels; k++) {
+        geom.push_back(level_geometry(W0, H0, prm, k));
+        OFC_REQUIRE(geom[k].w >= 1 && geom[k].h >= 1, "level %d of %d x %d is empty", k, W0, H0);
+    }
+    OFC_TRY(ensure_device(device));
+    float *outs[3] = {out1, out2, out3};
+    DevBuf src, dst[3];
+    OFC_TRY(src.alloc((size_t)n * W0 * H0));
+    for (int k = 1; k <= levels; k++) OFC_TRY(dst[k - 1].alloc(sizeof(float) * n * geom[k].w * geom[k].h));
+    OFC_HIP(hipMemcpy(src.p, frames, (size_t)n * W0 * H0, hipMemcpyHostToDevice));
+    const int L = fused ? pyramid_dec_levels(W0, H0, geom.data(), levels, true) : 0;
+    if (L >= 1) {
+        float *lv[3] = {dst[0].as<float>(), dst[1].as<float>(), dst[2].as<float>()};
+        OFC_TRY(launch_pyramid_dec(src.as<uint8_t>(), lv, n, W0, H0, geom.data(), L, nullptr));
+    }
+    for (int k = L + 1; k <= levels; k++)     // a level that is no exact decimation, and every deeper one: the per-level launches
+        OFC_TRY(launch_level_image(src.as<uint8_t>(), dst[k - 1].as<float>(), n, W0, H0, geom[k], nullptr));
+    for (int k = 1; k <= levels; k++)
+        OFC_HIP(hipMemcpy(outs[k - 1], dst[k - 1].p, sizeof(float) * n * geom[k].w * geom[k].h, hipMemcpyDeviceToHost));
+    if (fused_levels) *fused_levels = L;
+    return OFC_OK;
+}
+
+int ofc_pyramid_dec_geometry(int W0, int H0, int n, int *out4)
+{
+    OFC_REQUIRE(out4 && W0 >= 1 && H0 >= 1 && n >= 1, "bad arguments");
+    pyramid_dec_plan(W0, H0, n, out4[0], out4[1], out4[2], out4[3]);
     return OFC_OK;
 }
 
@@ -912,6 +978,47 @@ int ofc_bench_polyexp(int device, int W, int H, int n_images, int iters, int row
     hipStream_t s = own.s;
     auto launch = [&]() -> int { return launch_polyexp(I.as<float>(), R.as<float>(), n_images, W, H, pc, rows_per_block, s, true); };
     return time_launches(s, iters, launch, ms_per_launch);
+}
+
+int ofc_bench_pyramid_dec(int device, int W, int H, int n_images, int levels, int fused, int iters, float *ms_per_batch)
+{
+    OFC_REQUIRE(ms_per_batch && n_images >= 1 && iters >= 1 && levels >= 1 && levels <= 3, "bad arguments");
+    ofc_fb_params prm;
+    ofc_fb_default_params(&prm);
+    prm.levels = levels;
+    OFC_TRY(check_params(prm, W, H));
+    std::vector<LevelGeom> geom;
+    for (int k = 0; k <= levels; k++) geom.push_back(level_geometry(W, H, prm, k));
+    if (fused && pyramid_dec_levels(W, H, geom.data(), levels, true) != levels) {
+        set_error("levels 1..%d of %d x %d are not all exact decimations", levels, W, H);
+        return OFC_EUNSUPPORTED;
+    }
+    OFC_TRY(ensure_device(device));
+    const size_t P = (size_t)W * H;
+    DevBuf src, dst[3];
+    OFC_TRY(src.alloc(P * n_images));
+    for (int k = 1; k <= levels; k++) OFC_TRY(dst[k - 1].alloc(sizeof(float) * n_images * geom[k].w * geom[k].h));
+    {
+        std::vector<uint8_t> h(P);
+        uint32_t st = 12345u;
+        for (int im = 0; im < n_images; im++) {
+            for (size_t i = 0; i < P; i++) {
+                st = st * 1664525u + 1013904223u;
+                h[i] = (uint8_t)(st >> 24);
+            }
+            OFC_HIP(hipMemcpy(src.as<uint8_t>() + (size_t)im * P, h.data(), P, hipMemcpyHostToDevice));
+        }
+    }
+    ScopedStream own;
+    OFC_TRY(own.create());
+    hipStream_t s = own.s;
+    float *lv[3] = {dst[0].as<float>(), dst[1].as<float>(), dst[2].as<float>()};
+    auto launch = [&]() -> int {
+        if (fused) return launch_pyramid_dec(src.as<uint8_t>(), lv, n_images, W, H, geom.data(), levels, s);
+        for (int k = levels; k >= 1; k--) OFC_TRY(launch_level_image(src.as<uint8_t>(), lv[k - 1], n_images, W, H, geom[k], s));
+        return OFC_OK;
+    };
+    return time_launches(s, iters, launch, ms_per_batch);
 }
 
 }  // extern "C"

@@ -89,6 +89,12 @@ constexpr int WINSIZE_WIDE_MIN = 19;   // launch_box_solve: this winsize and wid
 // src: [nimg][H0][W0] u8 -> dst: [nimg][h][w] f32
 int launch_level_image(const uint8_t *src, float *dst, int nimg, int W0, int H0,
                        const LevelGeom &g, hipStream_t s);
+// levels 1..L of a batch in one launch (k_pyramid_dec): L = pyramid_dec_levels(...) says how many leading coarse levels
+// (geom[1..levels], three at the most) are exact decimations by 2, 4, 8; dst[k-1] takes level k as launch_level_image writes it
+int pyramid_dec_levels(int W0, int H0, const LevelGeom *geom, int levels, bool src_aligned);
+void pyramid_dec_plan(int W0, int H0, int nimg, int &bands, int &steps, int &sps, int &strips);
+int launch_pyramid_dec(const uint8_t *src, float *const *dst, int nimg, int W0, int H0, const LevelGeom *geom, int L,
+                       hipStream_t s);
 // level 0 fused into the polynomial expansion (frames u8 -> R), when the level is the plain 3x3 blur of the frame
 bool polyexp_u8_ok(int W, int H, const LevelGeom &g);
 int launch_polyexp_u8(const uint8_t *frames, float *R, int nimg, int W, int H, const PolyConsts &c, hipStream_t s);

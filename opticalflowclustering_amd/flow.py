@@ -69,6 +69,13 @@ class FlowEngine:
         check(load().ofc_flow_front_overlap(self._h, C.byref(on)))
         return bool(on.value)
 
+    def pyramid_fused(self):
+        """True when one launch per batch writes the level images of all coarse levels (overlap on, at most three coarse
+        levels, all exact decimations, OFC_PYRAMID_FUSED=0 not set at creation); the images are the same bits either way"""
+        on = C.c_int(-1)
+        check(load().ofc_flow_pyramid_fused(self._h, C.byref(on)))
+        return bool(on.value)
+
     def close(self):
         if getattr(self, "_h", None):
             load().ofc_flow_destroy(self._h)

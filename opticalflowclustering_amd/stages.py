@@ -17,6 +17,26 @@ def level_image(gray, k, params=None, device=0):
     return out.reshape(-1)[: w.value * h.value].reshape(h.value, w.value).copy()
 
 
+def pyramid_dec(frames, levels, fused=True, device=0):
+    """(images, fused_levels): the f32 images of pyramid levels 1..levels (pyr_scale 0.5) of u8 frames [n][H][W], each
+    [n][h][w]; fused: one k_pyramid_dec launch for the leading exact decimations (fused_levels of them) and the per-level
+    kernels for the rest, otherwise the per-level kernels throughout"""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, H, W = frames.shape
+    outs = [np.empty((n, int(np.rint(H * 0.5 ** k)), int(np.rint(W * 0.5 ** k))), np.float32) for k in range(1, levels + 1)]
+    ptrs = [ptr(o) for o in outs] + [None] * (3 - levels)
+    nf = C.c_int(-1)
+    check(load().ofc_pyramid_dec(device, ptr(frames), n, W, H, levels, int(bool(fused)), *ptrs, C.byref(nf)))
+    return outs, nf.value
+
+
+def pyramid_dec_geometry(W, H, n):
+    """(bands, steps, steps per strip, strips) of a k_pyramid_dec launch over n frames; needs no device"""
+    out = (C.c_int * 4)()
+    check(load().ofc_pyramid_dec_geometry(W, H, n, out))
+    return tuple(out)
+
+
 def polyexp(img, n=5, sigma=1.2, device=0):
     img = np.ascontiguousarray(img, np.float32)
     H, W = img.shape
@@ -81,6 +101,13 @@ def bench_flow_iters(W, H, n_pairs, reps, mode, device=0):
     """ms per batch for the last two iterations of a level (mode 0: two launches, mode 1: the two-iteration kernel)"""
     ms = C.c_float()
     check(load().ofc_bench_flow_iters(device, W, H, n_pairs, reps, mode, C.byref(ms)))
+    return ms.value
+
+
+def bench_pyramid_dec(W, H, n_images, levels=3, fused=True, iters=20, device=0):
+    """ms per batch of the level images 1..levels of n_images resident frames: one k_pyramid_dec launch or the per-level ones"""
+    ms = C.c_float()
+    check(load().ofc_bench_pyramid_dec(device, W, H, n_images, levels, int(bool(fused)), iters, C.byref(ms)))
     return ms.value
 
 
