@@ -107,6 +107,19 @@ int ofc_flow_calc_frames_dev(ofc_flow_t *f, const uint8_t *frames_dev, int n_fra
  * experimental kernels) form the same two sums with one sweep over the finished field: the call always succeeds. */
 int ofc_flow_calc_frames_dev_stats(ofc_flow_t *f, const uint8_t *frames_dev, int n_frames,
                                    float *flow_dev, double *uv_sum_dev);
+/* Both directions of every pair of the batch from ONE front end (level images and polynomial expansions depend on the frame
+ * alone) and one launch per iteration: fwd_dev[t] is what ofc_flow_calc_frames_dev defines; bwd_dev[t] is the flow from frame
+ * t+1 to frame t on frame t+1's grid, stored at t (NOT reversed: ofc_consist_dev takes the two with bwd_reversed = 0).  Both
+ * hold (n_frames-1) fields of HxWx2 f32.  Each field is, bit for bit, what a forward-only engine with max_batch >= 2(n_frames-1)
+ * gives for that pair of the palindrome clip f0 .. fn fn-1 .. f0 (pairs t and 2(n_frames-1)-1-t).
+ * The two buffers may lie anywhere: the last iteration of level 0 writes through two base pointers; they may not overlap.
+ * The first such call of an engine doubles its per-level flow scratch (and M with winsize > 15), which waits for the device
+ * once; an engine that never makes the call allocates nothing more.  With OFC_FLOW_GRAPH=1 the call makes plain launches.
+ * OFC_EINVAL: a null pointer, n_frames < 2, n_frames-1 > max_batch, overlapping buffers.  Asynchronous like the call above. */
+int ofc_flow_calc_frames_dev_bidir(ofc_flow_t *f, const uint8_t *frames_dev, int n_frames, float *fwd_dev, float *bwd_dev);
+/* As above, and uv_sum_dev[0..1] receive sum(u), sum(v) over the FORWARD fields (one sweep over the finished field). */
+int ofc_flow_calc_frames_dev_bidir_stats(ofc_flow_t *f, const uint8_t *frames_dev, int n_frames, float *fwd_dev,
+                                         float *bwd_dev, double *uv_sum_dev);
 int ofc_flow_sync(ofc_flow_t *f);
 /* *on = 1 when the engine runs the front end of the coarse pyramid levels (level images and polynomial expansions, which
  * depend on the frames only) on a side stream beside the level-0 expansion, 0 when it runs every level in series on one
@@ -189,6 +202,17 @@ int ofc_flow_iterate(int device, const float *R0, const float *R1, const float *
  * or n_pairs < 1, winsize even or outside 5 .. OFC_WINSIZE_MAX.  Test hook: the suite's case tables are checked against
  * these models themselves. */
 int ofc_flow_launch_geometry(int W, int H, int n_pairs, int winsize, int out[3]);
+/* Its twin for the fused iteration of ofc_flow_calc_frames_dev_bidir over n_pairs frame pairs (2 n_pairs logical pairs):
+ * out[0] rows per work-group, out[1] tiles (column tiles x strips) of one logical pair, out[2] work-groups of the launch
+ * (tiles rounded up to a multiple of 8, times 2 n_pairs).  Work-group b serves tile 8 (b / (16 n_pairs)) + b % 8 of logical
+ * pair q = (b % (16 n_pairs)) / 8: frame pair q >> 1, direction q & 1 (1 = backward).  Host only.  OFC_EINVAL: null pointer,
+ * W, H or n_pairs < 1, winsize even or outside 5 .. 15 (wider windows run the staged kernels). */
+int ofc_flow_launch_geometry_bidir(int W, int H, int n_pairs, int winsize, int out[3]);
+/* bench hook: *ms = average duration, by HIP events on the engine's stream over `reps` runs after two warm-up runs, of both
+ * directions of n_frames-1 synthetic pairs with the default parameters.  what 0: one ofc_flow_calc_frames_dev_bidir; what 1:
+ * the two-pass route, a forward-only call, the reversal of the frames and a second forward-only call on the same engine.
+ * Engine and buffers are allocated before the timed region. */
+int ofc_bench_flow_bidir(int device, int W, int H, int n_frames, int reps, int what, float *ms);
 /* bench hook: one 1080p-style level of `n_pairs` resident pairs, the last two of the three iterations of a level
  * timed with HIP events on their stream: mode 0 = two single-iteration launches, mode 1 = one two-iteration launch,
  * mode 2 = two launches of the 3-waves-per-SIMD kernel.
@@ -911,6 +935,19 @@ int ofc_stream_set_photo(ofc_stream_t *s, int on, int tau_q, int kappa_q, int ke
 /* The stats [n][5] of the n pairs the LAST finish delivered.  Valid under ofc_stream_read_blobs' conditions; max_pairs < n:
  * OFC_EINVAL, nothing written; OFC_EINVAL without the check.  No counterpart in the reference. */
 int ofc_stream_read_photo(ofc_stream_t *s, int64_t *stats_host, int max_pairs);
+/* A stream that checks its vectors forward-backward: from the next batch on, a batch's flow comes from
+ * ofc_flow_calc_frames_dev_bidir (both directions from one front end; the backward pair of a transition across two batches is
+ * in the later batch, which carries the earlier frame), and every pair is checked as ofc_consist_dev does with bwd_reversed
+ * = 0, directly behind the flow and BEFORE the repair, the moves and the camera; the counts go to a row per pair.  The state
+ * map then plays the role the photometric check's plays: the repair takes and updates it, and on a stream with blobs every
+ * pixel whose state is not in `keep` (1 .. 15) becomes background of the key map.  The stream keeps ONE state map: with the
+ * photometric check on, turning this one on is refused with OFC_EINVAL, and the other way round.  on = 0 removes the check and
+ * frees its buffers (a state map and a backward field of one batch).  Same precondition as ofc_stream_set_photo; alpha_q,
+ * beta_q as ofc_consist_check decides them for the stream's frame size.  No counterpart in the reference. */
+int ofc_stream_set_consist(ofc_stream_t *s, int on, int64_t alpha_q, int64_t beta_q, int keep);
+/* The counts [n][4] of the n pairs the LAST finish delivered.  Valid under ofc_stream_read_photo's conditions; max_pairs < n:
+ * OFC_EINVAL, nothing written; OFC_EINVAL without the check.  No counterpart in the reference. */
+int ofc_stream_read_consist(ofc_stream_t *s, int64_t *counts_host, int max_pairs);
 
 /* ---- Repair of a flow field: a masked median fill of the vectors that are not trusted, and a median smoothing pass.  What
  * the two checks above flag can so far only be thrown away; here a flagged vector is replaced by the component-wise median

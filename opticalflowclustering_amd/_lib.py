@@ -63,6 +63,8 @@ _PROTOS = {
     "ofc_flow_calc": ([_vp, _vp, _vp, _vp], _i),
     "ofc_flow_calc_frames_dev": ([_vp, _vp, _i, _vp], _i),
     "ofc_flow_calc_frames_dev_stats": ([_vp, _vp, _i, _vp, _vp], _i),
+    "ofc_flow_calc_frames_dev_bidir": ([_vp, _vp, _i, _vp, _vp], _i),
+    "ofc_flow_calc_frames_dev_bidir_stats": ([_vp, _vp, _i, _vp, _vp, _vp], _i),
     "ofc_flow_sync": ([_vp], _i),
     "ofc_flow_front_overlap": ([_vp, _ip], _i),
     "ofc_flow_pyramid_fused": ([_vp, _ip], _i),
@@ -77,6 +79,8 @@ _PROTOS = {
     "ofc_flow_resize": ([_i, _vp, _i, _i, _i, _i, _f, _vp], _i),
     "ofc_flow_iterate": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "ofc_flow_launch_geometry": ([_i, _i, _i, _i, _ip], _i),
+    "ofc_flow_launch_geometry_bidir": ([_i, _i, _i, _i, _ip], _i),
+    "ofc_bench_flow_bidir": ([_i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_pyramid_dec": ([_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ip], _i),
     "ofc_pyramid_dec_geometry": ([_i, _i, _i, _ip], _i),
     "ofc_bench_pyramid_dec": ([_i, _i, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
@@ -180,6 +184,8 @@ _PROTOS = {
     "ofc_bench_photo": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_stream_set_photo": ([_vp, _i, _i, _i, _i], _i),
     "ofc_stream_read_photo": ([_vp, _vp, _i], _i),
+    "ofc_stream_set_consist": ([_vp, _i, _i64, _i64, _i], _i),
+    "ofc_stream_read_consist": ([_vp, _vp, _i], _i),
     "ofc_repair_check": ([_i, _i, _i, _i, _i, _i, _i, _i], _i),
     "ofc_repair_tile": ([_i, C.POINTER(_i * 2)], None),
     "ofc_repair_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),

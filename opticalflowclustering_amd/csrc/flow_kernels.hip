@@ -1454,7 +1454,14 @@ __device__ __forceinline__ float2 upsampled_flow(const float2 *__restrict__ s, i
 // [block][wave][8] -- where a step's cycles go; never used by the engine
 // SUMS: also emit, per work-group, the f64 sums of the flow vectors it stores (`sums`: [grid][2]) -- the column sums Lloyd's
 // centring needs, taken from the last level-0 iteration's epilogue instead of from an extra 5 GB sweep over the clip
-template <int M, int UPS, bool STAMP = false, bool SUMS = false>
+// BIDIR: forward and backward flow of every pair from one launch (ofc_flow_calc_frames_dev_bidir).  `npair` is then the
+// LOGICAL count, twice the number of frame pairs: logical pair q is (pair q >> 1, direction q & 1), so the two work-groups
+// that read the same two R frames hold neighbouring same-XCD ids and march in step; the backward one swaps R0 and R1.
+// Every flow buffer holds the forward fields of all pairs, then the backward fields.  The two halves need not be adjacent
+// (level 0 ends in the caller's two buffers), and the argument block is the forward form's: the two pointers that only
+// STAMP and SUMS read carry the bases of the backward halves -- `dbg` that of flow_out, `sums` that of flow_in (the
+// coarse source with UPS).  The launch always sets both.
+template <int M, int UPS, bool STAMP = false, bool SUMS = false, bool BIDIR = false>
 __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ Rb, size_t frame_stride_R,
                                                       const float *__restrict__ flow_inb,
                                                       float *__restrict__ flow_outb, int W, int H,
@@ -1480,7 +1487,9 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
     // instead of HBM.  (speed only: any placement gives the same result)
     const int tiles = tiles_x * n_strips;
     const int group = blockIdx.x / (8 * npair), rem = blockIdx.x - group * (8 * npair);
-    const int pair = rem >> 3, tile = group * 8 + (rem & 7);
+    static_assert(!BIDIR || (!STAMP && !SUMS), "the bidirectional mode borrows the STAMP and SUMS pointers");
+    const int lpair = rem >> 3, tile = group * 8 + (rem & 7);
+    const int pair = BIDIR ? lpair >> 1 : lpair, dir = BIDIR ? lpair & 1 : 0;
     if (tile >= tiles) {
         if (SUMS && threadIdx.x < 2) sums[(size_t)blockIdx.x * 2 + threadIdx.x] = 0.0;     // padding work-group of the grid
         return;
@@ -1491,11 +1500,18 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
     const int y_begin = tile_y * rows_per_block;
     const int y_end = min(y_begin + rows_per_block, H);
     const size_t plane = (size_t)W * H;
-    const float *R0 = Rb + (size_t)pair * frame_stride_R;
-    const float *R1 = R0 + frame_stride_R;
-    const float2 *flow_in = UPS ? reinterpret_cast<const float2 *>(ups.src) + (size_t)pair * ups.sw * ups.sh
-                                : reinterpret_cast<const float2 *>(flow_inb) + (size_t)pair * plane;
-    float2 *flow_out = reinterpret_cast<float2 *>(flow_outb) + (size_t)pair * plane;
+    const float *R0 = Rb + (size_t)(pair + dir) * frame_stride_R;
+    const float *R1 = BIDIR ? Rb + (size_t)(pair + 1 - dir) * frame_stride_R : R0 + frame_stride_R;
+    // the direction's half of the two flow buffers (uniform: dir comes from the block id)
+    const float *inb = UPS ? ups.src : flow_inb;
+    float *outb = flow_outb;
+    if (BIDIR && dir) {
+        inb = reinterpret_cast<const float *>(sums);
+        outb = reinterpret_cast<float *>(dbg);
+    }
+    const float2 *flow_in = UPS ? reinterpret_cast<const float2 *>(inb) + (size_t)pair * ups.sw * ups.sh
+                                : reinterpret_cast<const float2 *>(inb) + (size_t)pair * plane;
+    float2 *flow_out = reinterpret_cast<float2 *>(outb) + (size_t)pair * plane;
     const int xc = min(max(x0 - M + tid, 0), W - 1);
     const int vs_w = ((tid >> 1) & 1) * PLD + 2 * (tid >> 2) + (tid & 1);     // this column's slot in a row of vs
     const double scale = 1.0 / ((2 * M + 1) * (2 * M + 1));
@@ -1882,6 +1898,55 @@ int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in
         else                                                                                             \
             hipLaunchKernelGGL((k_flow_iter<MM, 0>), grid, block, 0, s, R, frame_stride_R, flow_in,      \
                                flow_out, W, H, rows_per_block, u, tx, ns, npair);                        \
+        break;                                                                                           \
+    }
+    switch (winsize) {
+        OFC_FI_CASE(2)
+        OFC_FI_CASE(3)
+        OFC_FI_CASE(4)
+        OFC_FI_CASE(5)
+        OFC_FI_CASE(6)
+        OFC_FI_CASE(7)
+    default:
+        set_error("winsize %d unsupported by the fused iteration (odd 5..15)", winsize);
+        return OFC_EUNSUPPORTED;
+    }
+#undef OFC_FI_CASE
+    OFC_HIP(hipGetLastError());
+    return OFC_OK;
+}
+
+// One iteration of both directions of `npair` frame pairs (k_flow_iter<.., BIDIR>): 2 npair logical pairs in one grid, strips
+// sized for that work.  in/out/coarse: the forward and the backward half of each buffer, [npair] fields each; coarse_* null =
+// in_* is at this level's size.
+int launch_flow_iter_bidir(const float *R, size_t frame_stride_R, const float *in_fwd, const float *in_bwd, float *out_fwd,
+                           float *out_bwd, int npair, int W, int H, int winsize, hipStream_t s, const float *coarse_fwd,
+                           const float *coarse_bwd, int sw, int sh, float mul)
+{
+    OFC_TRY(flow_iter_check(W, H, winsize));
+    if (npair < 1 || npair > (1 << 20)) { set_error("bidirectional iteration: %d pairs", npair); return OFC_EINVAL; }
+    const int lp = 2 * npair;
+    const int rows_per_block = flow_iter_rows(W, H, lp, winsize);
+    UpsArgs u;
+    u.src = coarse_fwd; u.sw = sw; u.sh = sh; u.mul = mul;
+    u.scx = coarse_fwd ? (double)sw / W : 1.0; u.scy = coarse_fwd ? (double)sh / H : 1.0;
+    // the backward bases ride in the two pointer arguments the forward form leaves unused (see k_flow_iter)
+    unsigned long long *out_b = reinterpret_cast<unsigned long long *>(out_bwd);
+    double *in_b = reinterpret_cast<double *>(const_cast<float *>(coarse_fwd ? coarse_bwd : in_bwd));
+    dim3 block(256);
+#define OFC_FI_CASE(MM)                                                                                  \
+    case 2 * MM + 1: {                                                                                   \
+        const int tx = cdiv(W, 256 - 2 * MM), ns = cdiv(H, rows_per_block);                              \
+        dim3 grid(cdiv(tx * ns, 8) * 8 * lp);                                                            \
+        if (coarse_fwd && u.scx == 0.5 && u.scy == 0.5)                                                  \
+            hipLaunchKernelGGL((k_flow_iter<MM, 2, false, false, true>), grid, block, 0, s, R, frame_stride_R, in_fwd, \
+                               out_fwd, W, H, rows_per_block, u, tx, ns, lp, out_b, in_b);               \
+        else if (coarse_fwd)                                                                             \
+            hipLaunchKernelGGL((k_flow_iter<MM, 1, false, false, true>), grid, block, 0, s, R, frame_stride_R, in_fwd, \
+                               out_fwd, W, H, rows_per_block, u, tx, ns, lp, out_b, in_b);               \
+        else                                                                                             \
+            hipLaunchKernelGGL((k_flow_iter<MM, 0, false, false, true>), grid, block, 0, s, R, frame_stride_R, in_fwd, \
+                               out_fwd, W, H, rows_per_block, u, tx, ns, lp, out_b, in_b);               \
         break;                                                                                           \
     }
     switch (winsize) {

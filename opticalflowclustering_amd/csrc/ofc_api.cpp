@@ -1,6 +1,7 @@
 // ofc_api.cpp -- C ABI of libofc.so, part 1: runtime plumbing and the Farneback flow engine.
 // Declared in include/ofc.h (which cites the reference call each entry point replaces).
 #include "color_common.h"
+#include "fb_check.h"
 #include "host_util.h"
 #include "lloyd_common.h"
 
@@ -272,14 +273,56 @@ struct ofc_flow {
 
 namespace ofc {
 
-static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float *flow_dev, double *uv_sum_dev = nullptr)
+// A flow buffer of a batch as the iterations see it: the fields of the forward pairs at `f`; in a bidirectional run the
+// fields of the backward pairs at `b` (in the engine's scratch right behind the forward ones, at level 0 the caller's second
+// buffer), otherwise null.
+struct FlowHalves {
+    float *f = nullptr, *b = nullptr;
+    bool operator==(const FlowHalves &o) const { return f == o.f; }
+};
+
+static void flow_drop_graphs(ofc_flow *f)
+{
+    for (auto &g : f->graphs) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
+    }
+    f->graphs.clear();
+}
+
+// The first bidirectional call doubles the flow scratch (and M in staged mode): 2 max_batch fields per buffer.  The old
+// buffers are freed, which waits for the device; captured graphs hold their addresses and are dropped.
+static int flow_reserve_bidir(ofc_flow *f)
+{
+    const size_t P0 = (size_t)f->W * f->H, nb = 2 * (size_t)f->max_batch;
+    const size_t P1 = f->levels >= 1 ? (size_t)f->geom[1].w * f->geom[1].h : 1;
+    const size_t needAB = sizeof(float) * 2 * P1 * nb, needC = sizeof(float) * 2 * P0 * nb, needM = sizeof(float) * 5 * P0 * nb;
+    if (f->flowA.bytes >= needAB && f->flowB.bytes >= needAB && (f->fused ? f->flowC.bytes >= needC : f->M.bytes >= needM))
+        return OFC_OK;
+    if (!f->graphs.empty()) OFC_HIP(hipStreamSynchronize(f->stream));     // no replay in flight when its graph goes
+    flow_drop_graphs(f);
+    OFC_TRY(reserve(f->flowA, needAB));
+    OFC_TRY(reserve(f->flowB, needAB));
+    if (f->fused) OFC_TRY(reserve(f->flowC, needC));
+    else OFC_TRY(reserve(f->M, needM));
+    return OFC_OK;
+}
+
+// One batch: the front end of every level over the n_frames frames, then the iterations, coarsest level first.  With
+// bwd_dev the iterations run both directions of every pair (ofc_flow_calc_frames_dev_bidir): the front end is the same, every
+// flow buffer holds 2 npair fields, and the launches of the level loop cover both halves.
+static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float *flow_dev, double *uv_sum_dev = nullptr,
+                    float *bwd_dev = nullptr)
 {
     const int npair = n_frames - 1;
+    const bool bidir = bwd_dev != nullptr;
+    const int nfield = bidir ? 2 * npair : npair;
     const int W = f->W, H = f->H;
     hipStream_t s = f->stream;
     const int iters = f->prm.iterations;
-    float *prevFlow = nullptr;
+    FlowHalves prevFlow;
     int pw = 0, ph = 0;
+    if (bidir) OFC_TRY(flow_reserve_bidir(f));
     // a level's front end: level image and polynomial expansion of the batch's frames into the level's slices of I and R
     auto front_end = [&](int k, hipStream_t st) -> int {
         float *I = f->I.as<float>() + f->offI[k], *R = f->R.as<float>() + f->offR[k];
@@ -314,10 +357,20 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
     for (int k = f->levels; k >= 0; k--) {
         const LevelGeom &g = f->geom[k];
         const size_t P = (size_t)g.w * g.h;
-        // the level's final flow lands in `dst` (level 0: the caller's buffer); iterations ping-pong between
+        const size_t half = 2 * P * npair;              // floats of one direction's fields at this level
+        auto scratch = [&](DevBuf &b) { FlowHalves h; h.f = b.as<float>(); h.b = bidir ? h.f + half : nullptr; return h; };
+        auto adjacent = [&](const FlowHalves &h) { return h.b == h.f + half; };
+        auto zero = [&](const FlowHalves &h) -> int {
+            OFC_HIP(hipMemsetAsync(h.f, 0, sizeof(float) * half, s));
+            if (bidir) OFC_HIP(hipMemsetAsync(h.b, 0, sizeof(float) * half, s));
+            return OFC_OK;
+        };
+        // the level's final flow lands in `dst` (level 0: the caller's buffers); iterations ping-pong between
         // dst and tmp, so the initial flow goes to whichever makes the last iteration write dst
-        float *dst = (k == 0) ? flow_dev : (((f->levels - k) & 1) ? f->flowB.as<float>() : f->flowA.as<float>());
-        float *tmp = f->flowC.as<float>();
+        FlowHalves dst, tmp;
+        if (k == 0) { dst.f = flow_dev; dst.b = bwd_dev; }
+        else dst = scratch(((f->levels - k) & 1) ? f->flowB : f->flowA);
+        if (f->fused) tmp = scratch(f->flowC);
         const float *R = f->R.as<float>() + f->offR[k];
         if (!f->front_overlap) {
             OFC_TRY(front_end(k, s));
@@ -331,54 +384,75 @@ static int flow_run(ofc_flow *f, const uint8_t *frames_dev, int n_frames, float 
             // launch plan: the first iteration alone (it reads the coarser level directly -- upsample fused -- or, at the
             // top of the pyramid, a zeroed buffer), then two iterations per launch while the level is wide enough for the
             // two-iteration kernel's 228-column tiles, single launches otherwise.  Launch l of L writes dst when (L-1-l)
-            // is even, tmp otherwise, so that the last one lands in dst.
-            const bool two = f->fuse2 && f->prm.winsize == 15 && g.w >= f->fuse2_min_w;
+            // is even, tmp otherwise, so that the last one lands in dst.  (The bidirectional run has the plain kernel only.)
+            const bool two = !bidir && f->fuse2 && f->prm.winsize == 15 && g.w >= f->fuse2_min_w;
+            const bool w3 = !bidir && f->w3 && f->prm.winsize == 15 && g.w >= f->w3_min_w;
             int plan[64], L = 0;
             for (int i = 0; i < iters;) {
                 const int n = (two && i > 0 && iters - i >= 2) ? 2 : 1;
                 plan[L++] = n;
                 i += n;
             }
-            const float *cur = nullptr;
+            FlowHalves cur;
             for (int l = 0; l < L; l++) {
-                float *nxt = ((L - 1 - l) & 1) ? tmp : dst;
-                if (l == 0 && prevFlow) {
-                    OFC_TRY(launch_flow_iter(R, strideR, nullptr, nxt, npair, g.w, g.h, f->prm.winsize, s, prevFlow, pw, ph, mul));
+                const FlowHalves nxt = ((L - 1 - l) & 1) ? tmp : dst;
+                if (l == 0 && !prevFlow.f) {
+                    cur = (nxt == dst) ? tmp : dst;
+                    OFC_TRY(zero(cur));
+                }
+                const bool ups = l == 0 && prevFlow.f;
+                if (bidir) {
+                    OFC_TRY(launch_flow_iter_bidir(R, strideR, ups ? nullptr : cur.f, ups ? nullptr : cur.b, nxt.f, nxt.b, npair, g.w,
+                                                   g.h, f->prm.winsize, s, ups ? prevFlow.f : nullptr, ups ? prevFlow.b : nullptr,
+                                                   ups ? pw : 0, ups ? ph : 0, ups ? mul : 1.f));
+                } else if (ups) {
+                    OFC_TRY(launch_flow_iter(R, strideR, nullptr, nxt.f, npair, g.w, g.h, f->prm.winsize, s, prevFlow.f, pw, ph, mul));
                 } else {
-                    if (l == 0) {
-                        float *z = (nxt == dst) ? tmp : dst;
-                        OFC_HIP(hipMemsetAsync(z, 0, sizeof(float) * 2 * P * npair, s));
-                        cur = z;
-                    }
                     if (uv_sum_dev && k == 0 && l == L - 1 && plan[l] == 1 && f->prm.winsize == 15 && !(f->w3 && g.w >= f->w3_min_w)) {
                         // the field's column sums ride in the epilogue of the iteration that writes it
                         const size_t need = (size_t)flow_iter_max_grid(g.w, g.h, npair, f->prm.winsize) * 2;
                         OFC_TRY(reserve(f->uv_scratch, need * sizeof(double)));
                         // the launch is told what the buffer holds, not what this call needs: its own check then guards the records
-                        OFC_TRY(launch_flow_iter(R, strideR, cur, nxt, npair, g.w, g.h, f->prm.winsize, s, nullptr, 0, 0, 1.f,
+                        OFC_TRY(launch_flow_iter(R, strideR, cur.f, nxt.f, npair, g.w, g.h, f->prm.winsize, s, nullptr, 0, 0, 1.f,
                                                  uv_sum_dev, f->uv_scratch.as<double>(), f->uv_scratch.bytes / sizeof(double)));
                         uv_sum_dev = nullptr;
                     } else
-                    if (plan[l] == 2) OFC_TRY(launch_flow_iter2(R, strideR, cur, nxt, npair, g.w, g.h, f->prm.winsize, s));
-                    else if (f->w3 && f->prm.winsize == 15 && g.w >= f->w3_min_w)
-                        OFC_TRY(launch_flow_iter_w3(R, strideR, cur, nxt, npair, g.w, g.h, f->prm.winsize, s));
-                    else OFC_TRY(launch_flow_iter(R, strideR, cur, nxt, npair, g.w, g.h, f->prm.winsize, s));
+                    if (plan[l] == 2) OFC_TRY(launch_flow_iter2(R, strideR, cur.f, nxt.f, npair, g.w, g.h, f->prm.winsize, s));
+                    else if (w3) OFC_TRY(launch_flow_iter_w3(R, strideR, cur.f, nxt.f, npair, g.w, g.h, f->prm.winsize, s));
+                    else OFC_TRY(launch_flow_iter(R, strideR, cur.f, nxt.f, npair, g.w, g.h, f->prm.winsize, s));
                 }
                 cur = nxt;
             }
         } else {
-            float *cur = dst;
-            if (!prevFlow) {
-                OFC_HIP(hipMemsetAsync(cur, 0, sizeof(float) * 2 * P * npair, s));
+            // staged kernels, in place in dst.  Bidirectional: M holds 2 npair pairs, its second half filled with the frames
+            // swapped; the per-field kernels take both halves in one launch where the halves are adjacent (every level but
+            // 0), and in two launches of the same strip height otherwise
+            const FlowHalves cur = dst;
+            const bool one = !bidir || adjacent(cur);
+            if (!prevFlow.f) {
+                OFC_TRY(zero(cur));
+            } else if (one) {
+                OFC_TRY(launch_flow_resize(prevFlow.f, cur.f, nfield, pw, ph, g.w, g.h, mul, s));
             } else {
-                OFC_TRY(launch_flow_resize(prevFlow, cur, npair, pw, ph, g.w, g.h, mul, s));
+                OFC_TRY(launch_flow_resize(prevFlow.f, cur.f, npair, pw, ph, g.w, g.h, mul, s));
+                OFC_TRY(launch_flow_resize(prevFlow.b, cur.b, npair, pw, ph, g.w, g.h, mul, s));
             }
-            float *M = f->M.as<float>();
-            OFC_TRY(launch_update_matrices(R, R + strideR, strideR, cur, M, npair, g.w, g.h, s));
+            float *M = f->M.as<float>(), *Mb = M + 5 * P * npair;
+            const int box_rows = (bidir && f->prm.winsize < WINSIZE_WIDE_MIN) ? box_default_rows(g.w, g.h, nfield) : 0;
+            auto matrices = [&]() -> int {
+                OFC_TRY(launch_update_matrices(R, R + strideR, strideR, cur.f, M, npair, g.w, g.h, s));
+                if (bidir) OFC_TRY(launch_update_matrices(R + strideR, R, strideR, cur.b, Mb, npair, g.w, g.h, s));
+                return OFC_OK;
+            };
+            OFC_TRY(matrices());
             for (int i = 0; i < iters; i++) {
-                OFC_TRY(launch_box_solve(M, cur, npair, g.w, g.h, f->prm.winsize, 0, s));
-                if (i < iters - 1)
-                    OFC_TRY(launch_update_matrices(R, R + strideR, strideR, cur, M, npair, g.w, g.h, s));
+                if (one) {
+                    OFC_TRY(launch_box_solve(M, cur.f, nfield, g.w, g.h, f->prm.winsize, box_rows, s));
+                } else {
+                    OFC_TRY(launch_box_solve(M, cur.f, npair, g.w, g.h, f->prm.winsize, box_rows, s));
+                    OFC_TRY(launch_box_solve(Mb, cur.b, npair, g.w, g.h, f->prm.winsize, box_rows, s));
+                }
+                if (i < iters - 1) OFC_TRY(matrices());
             }
         }
         prevFlow = dst;
@@ -406,13 +480,7 @@ static int flow_run_cached(ofc_flow *f, const uint8_t *frames_dev, int n_frames,
     for (auto &g : f->graphs)
         if (g.frames == frames_dev && g.n_frames == n_frames && g.flow == flow_dev && g.uv_sum == uv_sum_dev) { c = &g; break; }
     if (!c) {
-        if (f->graphs.size() >= 64) {               // a caller that never repeats itself: stop bookkeeping
-            for (auto &g : f->graphs) {
-                if (g.exec) (void)hipGraphExecDestroy(g.exec);
-                if (g.graph) (void)hipGraphDestroy(g.graph);
-            }
-            f->graphs.clear();
-        }
+        if (f->graphs.size() >= 64) flow_drop_graphs(f);    // a caller that never repeats itself: stop bookkeeping
         f->graphs.emplace_back();
         c = &f->graphs.back();
         c->frames = frames_dev; c->n_frames = n_frames; c->flow = flow_dev; c->uv_sum = uv_sum_dev;
@@ -580,6 +648,29 @@ int ofc_flow_calc_frames_dev_stats(ofc_flow_t *f, const uint8_t *frames_dev, int
                 n_frames - 1, f->max_batch);
     OFC_TRY(ensure_device(f->device));
     return flow_run_cached(f, frames_dev, n_frames, flow_dev, uv_sum_dev);
+}
+
+static int flow_calc_bidir(ofc_flow_t *f, const uint8_t *frames_dev, int n_frames, float *fwd_dev, float *bwd_dev, double *uv_sum_dev)
+{
+    OFC_REQUIRE(f && frames_dev && fwd_dev && bwd_dev, "null pointer");
+    OFC_REQUIRE(n_frames >= 2 && n_frames - 1 <= f->max_batch, "n_frames-1 = %d pairs not in [1, max_batch=%d]",
+                n_frames - 1, f->max_batch);
+    const size_t half = 2 * (size_t)f->W * f->H * (size_t)(n_frames - 1);
+    OFC_REQUIRE(fwd_dev + half <= bwd_dev || bwd_dev + half <= fwd_dev, "fwd_dev and bwd_dev overlap");
+    OFC_TRY(ensure_device(f->device));
+    return flow_run(f, frames_dev, n_frames, fwd_dev, uv_sum_dev, bwd_dev);     // plain launches, also with graph replay on
+}
+
+int ofc_flow_calc_frames_dev_bidir(ofc_flow_t *f, const uint8_t *frames_dev, int n_frames, float *fwd_dev, float *bwd_dev)
+{
+    return flow_calc_bidir(f, frames_dev, n_frames, fwd_dev, bwd_dev, nullptr);
+}
+
+int ofc_flow_calc_frames_dev_bidir_stats(ofc_flow_t *f, const uint8_t *frames_dev, int n_frames, float *fwd_dev, float *bwd_dev,
+                                         double *uv_sum_dev)
+{
+    OFC_REQUIRE(uv_sum_dev, "null pointer");
+    return flow_calc_bidir(f, frames_dev, n_frames, fwd_dev, bwd_dev, uv_sum_dev);
 }
 
 hipStream_t ofc_flow_stream_internal(ofc_flow_t *f) { return f->stream; }   // for stream_api.cpp (not exported in ofc.h)
@@ -891,6 +982,42 @@ int ofc_flow_launch_geometry(int W, int H, int n_pairs, int winsize, int out[3])
     out[1] = winsize >= WINSIZE_WIDE_MIN ? box_wide_rows(winsize) : box_default_rows(W, H, n_pairs);
     out[2] = polyexp_default_rows(W, H, n_pairs + 1);
     return OFC_OK;
+}
+
+int ofc_flow_launch_geometry_bidir(int W, int H, int n_pairs, int winsize, int out[3])
+{
+    OFC_REQUIRE(out, "null pointer");
+    OFC_REQUIRE(W >= 1 && H >= 1 && n_pairs >= 1 && n_pairs <= (1 << 20), "bad size / pair count");
+    OFC_REQUIRE(winsize >= 5 && winsize <= 15 && (winsize & 1), "winsize must be odd, 5 .. 15 (the fused iteration)");
+    const int rows = flow_iter_rows(W, H, 2 * n_pairs, winsize);
+    out[0] = rows;
+    out[1] = cdiv(W, 256 - (winsize - 1)) * cdiv(H, rows);
+    out[2] = cdiv(out[1], 8) * 8 * 2 * n_pairs;
+    return OFC_OK;
+}
+
+int ofc_bench_flow_bidir(int device, int W, int H, int n_frames, int reps, int what, float *ms)
+{
+    OFC_REQUIRE(ms && n_frames >= 2 && reps >= 1 && (what == 0 || what == 1), "bad arguments");
+    ofc_flow_t *raw = nullptr;
+    OFC_TRY(ofc_flow_create(device, W, H, nullptr, n_frames - 1, &raw));
+    std::unique_ptr<ofc_flow, void (*)(ofc_flow_t *)> f(raw, ofc_flow_destroy);
+    const size_t P = (size_t)W * H, np = (size_t)(n_frames - 1);
+    DevBuf fr, rev, flow;
+    OFC_TRY(fr.alloc(P * n_frames));
+    OFC_TRY(rev.alloc(P * n_frames));
+    OFC_TRY(flow.alloc(sizeof(float) * 2 * P * np * 2));
+    OFC_TRY(ofc_synth_frames_dev(device, fr.as<uint8_t>(), W, H, n_frames, 0, 0));
+    OFC_HIP(hipDeviceSynchronize());
+    float *fwd = flow.as<float>(), *bwd = fwd + 2 * P * np;
+    auto run = [&]() -> int {
+        if (what == 0) return flow_run(f.get(), fr.as<uint8_t>(), n_frames, fwd, nullptr, bwd);
+        OFC_TRY(flow_run(f.get(), fr.as<uint8_t>(), n_frames, fwd));
+        OFC_TRY(launch_frames_reverse(fr.as<uint8_t>(), P, n_frames, rev.as<uint8_t>(), f->stream));
+        return flow_run(f.get(), rev.as<uint8_t>(), n_frames, bwd);
+    };
+    // (the first warm-up run also grows the bidirectional scratch: no allocation inside the timed region)
+    return time_launches(f->stream, reps, run, ms);
 }
 
 int ofc_bench_flow_iters(int device, int W, int H, int n_pairs, int reps, int mode, float *ms_out)

@@ -116,6 +116,12 @@ int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in
                      int npair, int W, int H, int winsize, hipStream_t s, const float *coarse = nullptr,
                      int sw = 0, int sh = 0, float mul = 1.f, double *uv_sum = nullptr, double *uv_scratch = nullptr,
                      size_t uv_scratch_doubles = 0, int rows_per_block = 0);
+// one iteration of both directions of npair frame pairs in one launch; every buffer comes as its forward and its backward
+// half ([npair] fields each, anywhere); strips are flow_iter_rows(W, H, 2 npair, winsize) high
+int launch_flow_iter_bidir(const float *R, size_t frame_stride_R, const float *in_fwd, const float *in_bwd, float *out_fwd,
+                           float *out_bwd, int npair, int W, int H, int winsize, hipStream_t s,
+                           const float *coarse_fwd = nullptr, const float *coarse_bwd = nullptr, int sw = 0, int sh = 0,
+                           float mul = 1.f);
 // strip height the cost model of the fused iteration picks for a level of this size and batch (a multiple of 16)
 int flow_iter_rows(int W, int H, int npair, int winsize);
 // upper bound of the iteration kernel's grid (work-groups) for a level of this size at that height: sizes the uv_scratch above

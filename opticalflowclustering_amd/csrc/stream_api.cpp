@@ -14,6 +14,9 @@
 // behind the flow, before the camera is subtracted (photo_check.hip); with blobs the key map is masked by the check's states.
 // With a repair (ofc_stream_set_repair) the batch's field is repaired in place directly behind that check, whose state map it
 // takes and updates (flow_repair.hip): before the moves are taken and the camera is fitted, so all of the above see it.
+// With a forward-backward check (ofc_stream_set_consist) the batch's flow comes from the engine's bidirectional call, which
+// also fills the stream's backward field; the check (fb_check.hip) runs where the photometric one would, and its state map
+// plays the same role for the repair and the blobs.  A stream has one of the two checks, not both.
 #include "blob_links.h"
 #include "color_common.h"
 #include "fb_check.h"
@@ -111,6 +114,15 @@ struct ofc_stream {
     DevBuf photo_state;                // one batch's state map, u8 [batch][H][W]
     PairTable photo_stats{sizeof(int64_t) * PHOTO_NSTAT};
     int photo_pairs = 0;               // pairs of the last finish: what ofc_stream_read_photo delivers
+    // the forward-backward check, when there is one (consist_on; never together with the photometric check): every pair's counts
+    bool consist_on = false;
+    int64_t consist_alpha = 0, consist_beta = 0;
+    int consist_keep = 0;
+    DevBuf consist_state;              // one batch's state map, u8 [batch][H][W]
+    DevBuf consist_bwd;                // one batch's backward field, f32 [batch][H][W][2]: one for the stream, the check reads it
+                                       // behind the flow on the compute stream before the next batch's flow can write it
+    PairTable consist_counts{sizeof(int64_t) * FB_NSTATE};
+    int consist_pairs = 0;             // pairs of the last finish: what ofc_stream_read_consist delivers
     // the repair, when there is one (repair_on): every pair's counts, kept past the finish like the photometric stats
     bool repair_on = false;
     int repair_keep = 0, repair_radius = 0, repair_rounds = 0, repair_min_count = 0, repair_smooth = 0;
@@ -135,6 +147,7 @@ void deliver(ofc_stream *s)
     s->cam_pairs = s->cam_kind ? s->pairs_submitted : 0;
     s->blob_pairs = s->blob_conn ? s->pairs_submitted : 0;
     s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
+    s->consist_pairs = s->consist_on ? s->pairs_submitted : 0;
     s->repair_pairs = s->repair_on ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
 }
@@ -180,11 +193,24 @@ int submit(ofc_stream *s, int i)
     if (s->blob_conn) { OFC_TRY(room(s->blob_table)); OFC_TRY(room(s->blob_found)); }
     if (s->link_max) { OFC_TRY(room(s->link_keys)); OFC_TRY(room(s->link_votes)); OFC_TRY(room(s->link_counters)); }
     if (s->photo_on) OFC_TRY(room(s->photo_stats));
+    if (s->consist_on) OFC_TRY(room(s->consist_counts));
     if (s->repair_on) OFC_TRY(room(s->repair_counts));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
-    OFC_TRY(ofc_flow_calc_frames_dev(s->flow, sl.frames.as<uint8_t>(), sl.n_frames, sl.flows.as<float>()));
+    // the state map of the stream's check, if it has one: the photometric or the forward-backward one
+    uint8_t *const check_state = s->photo_on ? s->photo_state.as<uint8_t>() : s->consist_on ? s->consist_state.as<uint8_t>() : nullptr;
+    const int check_keep = s->photo_on ? s->photo_keep : s->consist_keep;
+    if (s->consist_on) {
+        // both directions from one front end; the backward pair of a transition across two batches is in the later batch,
+        // which carries the earlier frame.  The check compares the whole flows: before the moves and the camera
+        OFC_TRY(ofc_flow_calc_frames_dev_bidir(s->flow, sl.frames.as<uint8_t>(), sl.n_frames, sl.flows.as<float>(),
+                                               s->consist_bwd.as<float>()));
+        OFC_TRY(launch_fb_check(sl.flows.as<float>(), s->consist_bwd.as<float>(), s->W, s->H, npair, false, s->consist_alpha,
+                                s->consist_beta, check_state, s->consist_counts.row<int64_t>(base), nullptr, s->compute));
+    } else {
+        OFC_TRY(ofc_flow_calc_frames_dev(s->flow, sl.frames.as<uint8_t>(), sl.n_frames, sl.flows.as<float>()));
+    }
     // the photometric check follows the whole flow into the slot's own next frame: before the camera is subtracted
     if (s->photo_on)
         OFC_TRY(launch_photo_check(sl.frames.as<uint8_t>(), sl.flows.as<float>(), s->W, s->H, npair, s->photo_tau, s->photo_kappa,
@@ -195,7 +221,7 @@ int submit(ofc_stream *s, int i)
         RepairScratch rs;
         rs.a = s->repair_a.as<float>(), rs.b = s->repair_b.as<float>(), rs.filled = s->repair_filled.as<uint8_t>();
         rs.chunk = repair_chunk_pairs(s->W, s->H, s->batch);
-        uint8_t *st = s->photo_on ? s->photo_state.as<uint8_t>() : nullptr;
+        uint8_t *st = check_state;
         OFC_TRY(launch_repair(sl.flows.as<float>(), st, s->W, s->H, npair, s->repair_keep, s->repair_radius, s->repair_rounds,
                               s->repair_min_count, s->repair_smooth != 0, sl.flows.as<float>(), nullptr, st,
                               s->repair_counts.row<int64_t>(base), rs, s->compute));
@@ -224,9 +250,9 @@ int submit(ofc_stream *s, int i)
         int *err = s->blob_err.as<int>();
         OFC_TRY(launch_blob_keys(sl.flows.as<float>(), s->W, s->H, npair, true, s->blob_thr, s->k ? s->model.as<LloydState>() : nullptr,
                                  s->k, (1u << s->k) - 1u, false, keys, s->compute));
-        // a pixel whose vector failed the photometric check belongs to no blob
-        if (s->photo_on)
-            OFC_TRY(launch_consist_mask(s->photo_state.as<uint8_t>(), (int64_t)P * npair, s->photo_keep, keys, nullptr, s->compute));
+        // a pixel whose vector failed the stream's check belongs to no blob
+        if (check_state)
+            OFC_TRY(launch_consist_mask(check_state, (int64_t)P * npair, check_keep, keys, nullptr, s->compute));
         OFC_TRY(launch_blob_local(keys, s->W, s->H, npair, s->blob_conn, labels, err, s->compute));
         OFC_TRY(launch_blob_seam(keys, s->W, s->H, npair, s->blob_conn, labels, err, s->compute));
         OFC_TRY(launch_blob_flatten(s->W, s->H, npair, labels, err, s->compute));
@@ -569,6 +595,7 @@ int ofc_stream_set_photo(ofc_stream_t *s, int on, int tau_q, int kappa_q, int ke
     if (on != 0) {
         OFC_TRY(photo_check(s->W, s->H, s->batch, tau_q, kappa_q));
         OFC_REQUIRE(keep >= 1 && keep < (1 << FB_NSTATE), "keep = %d: a set of the four states, 1 .. 15", keep);
+        OFC_REQUIRE(!s->consist_on, "the stream has a forward-backward check: one state map per stream, turn that off first");
     }
     OFC_TRY(require_idle(s, "set the photometric check on a fresh stream or straight after a finish"));
     OFC_TRY(ensure_device(s->device));
@@ -599,6 +626,48 @@ int ofc_stream_read_photo(ofc_stream_t *s, int64_t *stats_host, int max_pairs)
     OFC_REQUIRE(stats_host, "null pointer");
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
     OFC_HIP(hipMemcpy(stats_host, s->photo_stats.buf.p, s->photo_stats.per * (size_t)s->photo_pairs, hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+int ofc_stream_set_consist(ofc_stream_t *s, int on, int64_t alpha_q, int64_t beta_q, int keep)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (on != 0) {
+        OFC_TRY(fb_check(s->W, s->H, s->batch, alpha_q, beta_q));
+        OFC_REQUIRE(keep >= 1 && keep < (1 << FB_NSTATE), "keep = %d: a set of the four states, 1 .. 15", keep);
+        OFC_REQUIRE(!s->photo_on, "the stream has a photometric check: one state map per stream, turn that off first");
+    }
+    OFC_TRY(require_idle(s, "set the forward-backward check on a fresh stream or straight after a finish"));
+    OFC_TRY(ensure_device(s->device));
+    s->consist_pairs = 0;
+    if (on == 0) {
+        s->consist_state.release();
+        s->consist_bwd.release();
+        s->consist_counts.reset();
+        s->consist_on = false;
+        return OFC_OK;
+    }
+    const size_t n = (size_t)s->W * s->H * s->batch;
+    OFC_TRY(reserve(s->consist_state, n));
+    OFC_TRY(reserve(s->consist_bwd, sizeof(float) * 2 * n));
+    s->consist_on = true;
+    s->consist_alpha = alpha_q;
+    s->consist_beta = beta_q;
+    s->consist_keep = keep;
+    return OFC_OK;
+}
+
+int ofc_stream_read_consist(ofc_stream_t *s, int64_t *counts_host, int max_pairs)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->consist_on, "the stream has no forward-backward check (ofc_stream_set_consist)");
+    OFC_TRY(require_idle(s, "read the forward-backward counts straight after a finish"));
+    OFC_REQUIRE(max_pairs >= s->consist_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->consist_pairs);
+    OFC_TRY(ensure_device(s->device));
+    if (!s->consist_pairs) return OFC_OK;
+    OFC_REQUIRE(counts_host, "null pointer");
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    OFC_HIP(hipMemcpy(counts_host, s->consist_counts.buf.p, s->consist_counts.per * (size_t)s->consist_pairs, hipMemcpyDeviceToHost));
     return OFC_OK;
 }
 

@@ -58,6 +58,20 @@ class FlowEngine:
         if sync:
             self.sync()
 
+    def calc_frames_dev_bidir(self, frames_ptr, n_frames, fwd_ptr, bwd_ptr, sync=True, uv_sum_ptr=None):
+        """device pointers: n_frames resident u8 frames -> n_frames-1 forward flows at fwd_ptr and n_frames-1 backward flows
+        at bwd_ptr from one front end (ofc_flow_calc_frames_dev_bidir): bwd[t] is the flow from frame t+1 to frame t, stored
+        at t (consistency.check_dev takes it with bwd_reversed=False).  The buffers may not overlap.  uv_sum_ptr: device
+        address of two doubles that receive sum(u), sum(v) of the forward flows"""
+        if uv_sum_ptr:
+            check(load().ofc_flow_calc_frames_dev_bidir_stats(self._h, C.c_void_p(frames_ptr), n_frames, C.c_void_p(fwd_ptr),
+                                                              C.c_void_p(bwd_ptr), C.c_void_p(uv_sum_ptr)))
+        else:
+            check(load().ofc_flow_calc_frames_dev_bidir(self._h, C.c_void_p(frames_ptr), n_frames, C.c_void_p(fwd_ptr),
+                                                        C.c_void_p(bwd_ptr)))
+        if sync:
+            self.sync()
+
     def sync(self):
         check(load().ofc_flow_sync(self._h))
 

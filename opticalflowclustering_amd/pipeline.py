@@ -60,6 +60,7 @@ class ClipPipeline:
         self._compensated = False           # compensate_camera() has run since the last run_flow()
         self.frames_rev = None              # run_backward_flow(): the resident frames in reverse order, n_frames * P u8
         self.flows_bwd = None               # ... and the field of that clip: pair t's backward field at n_pairs-1-t
+        self.bwd_reversed = True            # False after run_flow_bidirectional(): pair t's backward field at t
         self.state = None                   # consistency() / photometric(): the state map of the check that ran last, n_pairs * P u8
         self.filled = None                  # repair(): the round every pixel was filled in, n_pairs * P u8
 
@@ -110,6 +111,7 @@ class ClipPipeline:
         self._drop_backward()
         self.frames_rev = DeviceBuffer(self.n_frames * P, self.device)
         self.flows_bwd = DeviceBuffer(self.n_pairs * P * 8, self.device)
+        self.bwd_reversed = True
         cons.frames_reverse_dev(self.frames.ptr, self.W, self.H, self.n_frames, self.frames_rev.ptr, self.device)
         p0 = 0
         for i, n in enumerate(self.schedule):
@@ -119,15 +121,43 @@ class ClipPipeline:
         if sync:
             self.sync()
 
+    def run_flow_bidirectional(self, sync=True):
+        """run_flow() and the backward field of every pair from ONE front end (FlowEngine.calc_frames_dev_bidir): the same
+        batch schedule on the same engines, forward fields into the resident field as run_flow() leaves them, backward fields
+        into flows_bwd in the clip's own order (pair t's at t: the library's bwd_reversed = 0, which consistency() then
+        passes).  The column sums for run_kmeans come from a sweep over each batch's finished forward field.  As much memory
+        again for the field; the next run_flow() discards it."""
+        P = self.W * self.H
+        self.sync()
+        self._drop_backward()
+        self.flows_bwd = DeviceBuffer(self.n_pairs * P * 8, self.device)
+        p0 = 0
+        for i, n in enumerate(self.schedule):
+            self.engines[i % len(self.engines)].calc_frames_dev_bidir(self.frames.ptr + p0 * P, n + 1, self.flows.ptr + p0 * P * 8,
+                                                                      self.flows_bwd.ptr + p0 * P * 8, sync=False,
+                                                                      uv_sum_ptr=self.uv_sums.ptr + 16 * i)
+            p0 += n
+        self.bwd_reversed = False
+        self._sums_valid = True
+        self._label_k = None                # as run_flow(): labels, camera and moves belonged to the overwritten field
+        self._compensated = False
+        if self.moves is not None:
+            self.moves.free()
+            self.moves = None
+        if sync:
+            self.sync()
+
     def flows_bwd_host(self):
-        """host copy of run_backward_flow()'s field, in the order it has on the device (the reversed clip's)"""
+        """host copy of the backward field in the order it has on the device: the reversed clip's after run_backward_flow()
+        (pair t's at n_pairs-1-t), the clip's own after run_flow_bidirectional() (pair t's at t); bwd_reversed says which"""
         if self.flows_bwd is None:
             raise ValueError("no backward field: call run_backward_flow() first (run_flow() discards it)")
         self.sync()
         return self.flows_bwd.download((self.n_pairs, self.H, self.W, 2), np.float32)
 
     def consistency(self, alpha=0.01, beta=0.5, residual=False):
-        """the forward-backward check of the resident field against run_backward_flow()'s (consistency.py; ofc_consist_dev)
+        """the forward-backward check of the resident field against the backward field of run_backward_flow() or
+        run_flow_bidirectional(), in whichever order that left it (consistency.py; ofc_consist_dev)
         -> consistency.Consistency.  The state map also stays on the device, for blobs(consistent=True) and
         run_kmeans / seed_kmeans(consistent=True), until the next run_flow().  alpha, beta: consistency.check's, a
         convention of the literature and not tuned here.  ValueError without a backward field, and after
@@ -146,7 +176,7 @@ class ClipPipeline:
             self.state = DeviceBuffer(n * W * H, self.device)
         try:
             counts, resid = cons.check_dev(self.flows.ptr, self.flows_bwd.ptr, W, H, n, self.state.ptr, alpha_q, beta_q,
-                                           bwd_reversed=True, residual=residual, device=self.device)
+                                           bwd_reversed=self.bwd_reversed, residual=residual, device=self.device)
         except Exception:
             self.state.free()
             self.state = None

@@ -97,6 +97,22 @@ def flow_launch_geometry(W, H, n_pairs, winsize=15):
     return tuple(out)
 
 
+def flow_launch_geometry_bidir(W, H, n_pairs, winsize=15):
+    """(rows of k_flow_iter, tiles of one logical pair, work-groups of the launch) of the bidirectional iteration over
+    n_pairs frame pairs (ofc_flow_launch_geometry_bidir); needs no device"""
+    out = (C.c_int * 3)()
+    check(load().ofc_flow_launch_geometry_bidir(W, H, n_pairs, winsize, out))
+    return tuple(out)
+
+
+def bench_flow_bidir(W, H, n_frames, reps, what, device=0):
+    """ms per batch for both directions of n_frames - 1 pairs (what 0: one bidirectional call; 1: two forward-only calls,
+    the second on the reversed frames)"""
+    ms = C.c_float()
+    check(load().ofc_bench_flow_bidir(device, W, H, n_frames, reps, what, C.byref(ms)))
+    return ms.value
+
+
 def bench_flow_iters(W, H, n_pairs, reps, mode, device=0):
     """ms per batch for the last two iterations of a level (mode 0: two launches, mode 1: the two-iteration kernel)"""
     ms = C.c_float()

@@ -12,7 +12,10 @@ with max_links among them the blobs of consecutive pairs are linked too, inside 
 With a photometric check (photometric=True or dict(tau=, kappa=, keep=)) every pair's vectors are checked against the batch's
 own frames (photometric.py): photometric_stats(), and the blobs keep only the pixels that passed.
 With a repair (repair=True or dict(radius=, rounds=, min_count=, smooth=, keep=)) the vectors that check flagged are filled
-in by the median of their trusted neighbours before anything else looks at the field (repair.py): repair_stats()."""
+in by the median of their trusted neighbours before anything else looks at the field (repair.py): repair_stats().
+With a forward-backward check (consistency=True or dict(alpha=, beta=, keep=)) every batch's flow is computed in both
+directions from one front end and every pair's vectors are checked against the flow back (consistency.py):
+consistency_stats(); the repair and the blobs use its states as they use the photometric check's.  One check per stream."""
 import ctypes as C
 
 import numpy as np
@@ -22,7 +25,7 @@ from ._lib import FbParams, check, load, ptr
 
 class FlowStream:
     def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False,
-                 histogram=None, camera=None, blobs=None, photometric=None, repair=None):
+                 histogram=None, camera=None, blobs=None, photometric=None, repair=None, consistency=None):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
@@ -46,9 +49,39 @@ class FlowStream:
         self.photo_args = None              # (tau_q, kappa_q, keep) of the stream's photometric check, or None
         if photometric is not None and photometric is not False:
             self.set_photometric(**({} if photometric is True else photometric))
+        self.consist_args = None            # (alpha_q, beta_q, keep) of the stream's forward-backward check, or None
+        if consistency is not None and consistency is not False:
+            self.set_consistency(**({} if consistency is True else consistency))
         self.repair_args = None             # (keep, radius, rounds, min_count, smooth) of the stream's repair, or None
         if repair is not None and repair is not False:
             self.set_repair(**({} if repair is True else repair))
+
+    def set_consistency(self, alpha=None, beta=None, keep=(0,), on=True):
+        """from the next batch on, compute every batch's flow in both directions from one front end
+        (FlowEngine.calc_frames_dev_bidir) and put every pair's vectors to the forward-backward check (ofc_stream_set_consist;
+        consistency.py has the definition), directly behind the flow and before the repair, the moves and a camera.  Its
+        states then do what the photometric check's do: the repair fills what is not in `keep` (consistency.keep_mask), and
+        on a stream with blobs those pixels belong to no blob.  A stream has one of the two checks: ValueError when the
+        photometric one is on (and from set_photometric when this one is).  on=False removes it.  alpha and beta default to
+        consistency.ALPHA and BETA.  Only on a stream that holds no frame and no undelivered result, as set_model;
+        ValueError otherwise, and nothing changes."""
+        if not on:
+            check(load().ofc_stream_set_consist(self._h, 0, 0, 0, 0))
+            self.consist_args, self._last_pairs = None, 0
+            return
+        from . import consistency as K
+        args = K.quantise(K.ALPHA if alpha is None else alpha, K.BETA if beta is None else beta) + (K.keep_mask(keep),)
+        check(load().ofc_stream_set_consist(self._h, 1, *args))
+        self.consist_args, self._last_pairs = args, 0
+
+    def consistency_stats(self):
+        """-> (n, 4) int64 of the pairs the last finish() / finish_clusters() delivered (ofc_stream_read_consist): the pixels
+        in each of the four states.  Straight after a finish only; ValueError once frames are held again, and on a stream
+        without the check."""
+        n = self._last_pairs
+        counts = np.zeros((max(n, 1), 4), np.int64)
+        check(load().ofc_stream_read_consist(self._h, ptr(counts), max(n, 1)))
+        return counts[:n]
 
     def set_repair(self, radius=1, rounds=8, min_count=1, smooth=False, keep=(0,), on=True):
         """from the next batch on, repair every batch's field in place (ofc_stream_set_repair; repair.py has the definition)
