@@ -1022,6 +1022,85 @@ int ofc_stream_set_repair(ofc_stream_t *s, int on, int keep, int radius, int rou
  * OFC_EINVAL, nothing written; OFC_EINVAL without the repair. */
 int ofc_stream_read_repair(ofc_stream_t *s, int64_t *counts_host, int max_pairs);
 
+/* ---- Trajectories: points followed through a clip's flow fields (dense trajectories, particle advection).  Every other
+ * temporal object of the library is a vote on whole-pixel moves between two label maps (the blob links); here a point
+ * placed anywhere is carried from pair to pair by the bilinearly interpolated flow at its sub-pixel position, until it
+ * leaves the frame or the vector under it cannot be trusted.  The reference has no counterpart: its motion signature over
+ * time was a per-cell mean (drawGridsAndOutputCSV.py), it never followed a point.
+ * Definition (normative, like the text above; every output is an integer and does not depend on the order of the work).
+ * Inputs: flow f32 [npair][H][W][2]; seeds int32 [P][2] holding (X, Y) in 1/65536 px, any int32 allowed; optionally state
+ * u8 [npair][H][W] with a set `keep` (bit s = state s) as ofc_consist_mask_dev reads it.  Q(u) and "valid vector" are
+ * exactly the consistency block's: u, v finite, |u|, |v| < 1024, Q(u) = llrint((double)u * 65536).
+ * Step t = 0 .. npair-1 of a live point at (X, Y), decided in this order:
+ * 1. The point is inside iff 0 <= X <= (W-1) << 16 and 0 <= Y <= (H-1) << 16.  If it is not, it ends with OFC_TRAJ_LEAVES
+ *    (only a seed at t = 0 can: rule 4 keeps every later position inside).
+ * 2. With a state map: rx = (X + 32768) >> 16, ry = (Y + 32768) >> 16, the nearest pixel, inside by rule 1;
+ *    s = state[t][ry][rx]; if s > 3 or bit s of keep is clear, the point ends with OFC_TRAJ_UNTRUSTED.
+ * 3. ix = X >> 16, fx = X & 65535, iy and fy likewise.  The four taps of flow[t] are (ix, iy), (min(ix+1, W-1), iy),
+ *    (ix, min(iy+1, H-1)), (min(ix+1, W-1), min(iy+1, H-1)) with the weights (65536-fx)(65536-fy), fx(65536-fy),
+ *    (65536-fx)fy, fx*fy (they sum to 2^32).  If any of the four is not a valid vector (whatever its weight), the point ends
+ *    with OFC_TRAJ_INVALID.
+ * 4. Per component S = sum of w_i * Q(f_i) in int64 (|S| <= 2^58), D = (S + 2^31) >> 32 with an arithmetic shift;
+ *    X' = X + Dx, Y' = Y + Dy (int32: X < 2^30, |D| < 2^26).  If (X', Y') is not inside, the point ends with
+ *    OFC_TRAJ_LEAVES and does not move; otherwise it moves there and the step counts.
+ * Outputs: pos int32 [npair+1][P][2], time-major: pos[0] is the seeds, pos[t+1][p] the position after step t if that step
+ * was taken and pos[t][p] otherwise (an ended point stays where it ended).  len int32 [P]: the steps taken, 0 .. npair.  why u8
+ * [P]: one of the OFC_TRAJ_* below; they are the consistency states' own numbers wherever they mean the same thing.
+ * Limits: W, H in 1 .. 16384 (above: OFC_EUNSUPPORTED); npair in 1 .. 65535; P in 1 .. 2^28; keep in 0 .. 65535;
+ * pairs_per_launch >= 0; everything else OFC_EINVAL.
+ * Safety: every index, the state byte's and the taps of ended points included, is clamped into the frame before it indexes
+ * anything, whatever seeds and fields hold; no loop has a data-dependent trip count. ---- */
+#define OFC_TRAJ_RAN 0        /* the point took all npair steps */
+#define OFC_TRAJ_UNTRUSTED 1  /* the state under it is not in keep */
+#define OFC_TRAJ_LEAVES 2     /* it is, or would land, outside the frame */
+#define OFC_TRAJ_INVALID 3    /* one of the four taps is not a valid vector */
+#define OFC_TRAJ_THREADS 256  /* points a work-group of the kernel takes */
+#define OFC_TRAJ_MAX_POINTS (1 << 28)
+#define OFC_TRAJ_ONE_LAUNCH_POINTS (1 << 19)  /* the cost model: up to this many points all pairs go into one launch ... */
+#define OFC_TRAJ_DENSE_PAIRS 16               /* ... and above it this many pairs per launch (see ofc_traj_launch_geometry) */
+/* Host only, no device is touched: OFC_OK iff the arguments are inside the limits above.  Every call below decides by it
+ * before anything is allocated or launched.  No counterpart in the reference, as for every call of this block. */
+int ofc_traj_check(int W, int H, int npair, int64_t P, int keep, int pairs_per_launch);
+/* Host only: how ofc_traj_dev cuts the pairs into launches when pairs_per_launch is 0.  out[0] = the pairs per launch (the
+ * last launch takes what is left), out[1] = the work-groups per launch (ceil(P / OFC_TRAJ_THREADS)), out[2] = the launches
+ * (ceil(npair / out[0])), out[3] = the lanes per work-group.  The model: a launch keeps a point's position in registers
+ * over its pairs, so with few points (P <= OFC_TRAJ_ONE_LAUNCH_POINTS, the lanes the device holds at once) one launch over
+ * all pairs saves npair - 1 launches of a latency-bound loop; with more points than that the work-groups come in rounds and
+ * out[0] = min(npair, OFC_TRAJ_DENSE_PAIRS).  Measured on the MI355X at 1920x1080 x 16 pairs, longer chunks were
+ * faster up to 16 pairs in both regimes; no longer chunk was timed with dense seeds, so that is where the constant stands.  The result of ofc_traj_dev is the same bits for every choice.  Refusals as
+ * ofc_traj_check (keep 0, pairs_per_launch 0), and OFC_EINVAL for out NULL.  No counterpart in the reference. */
+int ofc_traj_launch_geometry(int W, int H, int npair, int64_t P, int out[4]);
+/* flow_dev f32 [npair][H][W][2] (8-byte aligned), state_dev u8 [npair][H][W] or NULL, seeds_dev int32 [P][2] -> pos_dev int32
+ * [npair+1][P][2] (8-byte aligned), len_dev int32 [P] (4-byte aligned), why_dev u8 [P].  pairs_per_launch 0: as
+ * ofc_traj_launch_geometry says; a positive value forces the chunk, one above npair means npair.  Between launches the
+ * table is the carry: a point is live at step t iff len[p] == t.  seeds_dev may be row 0 of pos_dev (then nothing is
+ * copied); otherwise it must not overlap pos_dev.  Neither input is written.  Returns when done.  No counterpart in the
+ * reference. */
+int ofc_traj_dev(int device, const float *flow_dev, const uint8_t *state_dev, int W, int H, int npair, const int32_t *seeds_dev,
+                 int64_t P, int keep, int pairs_per_launch, int32_t *pos_dev, int32_t *len_dev, uint8_t *why_dev);
+/* The whole chain on host buffers of the same shapes; state_host may be NULL.  No counterpart in the reference. */
+int ofc_traj(int device, const float *flow_host, const uint8_t *state_host, int W, int H, int npair, const int32_t *seeds_host,
+             int64_t P, int keep, int pairs_per_launch, int32_t *pos_host, int32_t *len_host, uint8_t *why_host);
+/* Measurement hook: average duration by HIP events over `iters` runs of the whole chain (the clears of len and why, the copy
+ * of the seeds, every launch), two warm-up runs before them, on flow_dev and seeds_dev without a state map, with outputs of
+ * the hook's own that are allocated before the timed region.  No counterpart in the reference. */
+int ofc_bench_traj(int device, const float *flow_dev, int W, int H, int npair, const int32_t *seeds_dev, int64_t P,
+                   int pairs_per_launch, int iters, float *ms_per_run);
+/* A stream that follows points: the P seeds (int32 [P][2], copied here) are placed at the first pair after this call or
+ * after a finish, and every batch's advection runs directly behind the repair and BEFORE the moves and the camera (a point
+ * lands by the WHOLE flow: the rule of the moves), one launch per batch; the last row written is the carry into the next
+ * batch.  use_state != 0: a point ends where the state map of the stream's check (photometric or forward-backward, as the
+ * repair left it) is not in that check's keep; without a check on the stream OFC_EINVAL.  P = 0 removes the stage: the
+ * stream then launches exactly what a stream that never had one launches.  Same precondition as ofc_stream_set_photo; P as
+ * ofc_traj_check decides it for the stream's frame size.  A check that is removed while use_state is set makes the next
+ * batch fail with OFC_EINVAL.  No counterpart in the reference. */
+int ofc_stream_set_traj(ofc_stream_t *s, int64_t P, const int32_t *seeds_host, int use_state);
+/* pos [n+1][P][2], len [P], why [P] of the n pairs the LAST finish delivered (a finish ends the clip: the next clip starts
+ * from the seeds again).  Valid under ofc_stream_read_photo's conditions; max_pairs < n: OFC_EINVAL, nothing written;
+ * OFC_EINVAL without the stage.  A why of OFC_TRAJ_RAN says the point was still live when the clip ended.  No counterpart in
+ * the reference. */
+int ofc_stream_read_traj(ofc_stream_t *s, int32_t *pos_host, int32_t *len_host, uint8_t *why_host, int max_pairs);
+
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.

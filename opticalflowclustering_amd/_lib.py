@@ -23,6 +23,9 @@ CONSIST_SHARE, CONSIST_MAX_DIM = 2048, 16384         # OFC_CONSIST_SHARE, OFC_CO
 CONSIST_ALPHA_MAX, CONSIST_BETA_MAX = 65536, 1 << 62  # OFC_CONSIST_ALPHA_MAX, OFC_CONSIST_BETA_MAX
 PHOTO_SHARE, PHOTO_TAU_MAX, PHOTO_KAPPA_MAX, PHOTO_NSTAT = 2048, 65280, 1024, 5      # OFC_PHOTO_*
 REPAIR_ROUNDS_MAX, REPAIR_NCOUNT, REPAIR_UNFILLED = 254, 3, 255                      # OFC_REPAIR_*
+TRAJ_RAN, TRAJ_UNTRUSTED, TRAJ_LEAVES, TRAJ_INVALID = 0, 1, 2, 3                     # OFC_TRAJ_*: why a point ended
+TRAJ_THREADS, TRAJ_MAX_POINTS = 256, 1 << 28                                         # OFC_TRAJ_THREADS, OFC_TRAJ_MAX_POINTS
+TRAJ_ONE_LAUNCH_POINTS, TRAJ_DENSE_PAIRS = 1 << 19, 16                               # the launch model's two constants
 
 
 class OfcError(RuntimeError):
@@ -193,6 +196,13 @@ _PROTOS = {
     "ofc_bench_repair": ([_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_f)], _i),
     "ofc_stream_set_repair": ([_vp, _i, _i, _i, _i, _i, _i], _i),
     "ofc_stream_read_repair": ([_vp, _vp, _i], _i),
+    "ofc_traj_check": ([_i, _i, _i, _i64, _i, _i], _i),
+    "ofc_traj_launch_geometry": ([_i, _i, _i, _i64, C.POINTER(_i * 4)], _i),
+    "ofc_traj_dev": ([_i, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp], _i),
+    "ofc_traj": ([_i, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp], _i),
+    "ofc_bench_traj": ([_i, _vp, _i, _i, _i, _vp, _i64, _i, _i, C.POINTER(_f)], _i),
+    "ofc_stream_set_traj": ([_vp, _i64, _vp, _i], _i),
+    "ofc_stream_read_traj": ([_vp, _vp, _vp, _vp, _i], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

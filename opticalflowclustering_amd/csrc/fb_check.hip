@@ -23,22 +23,6 @@ static_assert(FB_PASSES * FB_RUN * 64 < 65536, "a wave's counts fit their 16-bit
 typedef unsigned long long u64;
 typedef long long i64;
 
-struct FbVec {
-    int qu, qv;
-    bool valid;
-};
-
-// the camera and blob blocks' test and quantisation (motion_model.hip, blobs.hip): an invalid vector quantises to 0
-__device__ __forceinline__ FbVec fb_quantise(float2 f)
-{
-    const bool valid = fabsf(f.x) < 1024.f && fabsf(f.y) < 1024.f;     // NaN and inf fail
-    FbVec q;
-    q.qu = valid ? __double2int_rn((double)f.x * 65536.0) : 0;
-    q.qv = valid ? __double2int_rn((double)f.y * 65536.0) : 0;
-    q.valid = valid;
-    return q;
-}
-
 __device__ __forceinline__ unsigned fb_wave_add(unsigned v)
 {
 #pragma unroll

@@ -17,6 +17,8 @@
 // With a forward-backward check (ofc_stream_set_consist) the batch's flow comes from the engine's bidirectional call, which
 // also fills the stream's backward field; the check (fb_check.hip) runs where the photometric one would, and its state map
 // plays the same role for the repair and the blobs.  A stream has one of the two checks, not both.
+// With trajectories (ofc_stream_set_traj) the stream's points are advected through every batch's field directly behind the
+// repair, before the moves and the camera (trajectories.hip): one launch per batch, the last row of the table is the carry.
 #include "blob_links.h"
 #include "color_common.h"
 #include "fb_check.h"
@@ -25,6 +27,7 @@
 #include "lloyd_common.h"
 #include "motion_model.h"
 #include "photo_check.h"
+#include "trajectories.h"
 
 #include <memory>
 
@@ -129,6 +132,12 @@ struct ofc_stream {
     DevBuf repair_a, repair_b, repair_filled;   // the snapshots and the filled map of a chunk of a batch (RepairScratch)
     PairTable repair_counts{sizeof(int64_t) * REPAIR_NCOUNT};
     int repair_pairs = 0;              // pairs of the last finish: what ofc_stream_read_repair delivers
+    // the trajectories, when there are any (traj_P > 0): the positions after every pair, kept past the finish like the camera's fits
+    int64_t traj_P = 0;
+    bool traj_use_state = false;       // a point ends where the check's state map is not in the check's keep
+    DevBuf traj_seeds, traj_len, traj_why;   // int32 [P][2], int32 [P], u8 [P]
+    PairTable traj_pos;                // int32 [P][2] per pair: the positions after it; the last row written is the carry
+    int traj_pairs = 0;                // pairs of the last finish: what ofc_stream_read_traj delivers
 };
 
 namespace {
@@ -149,6 +158,7 @@ void deliver(ofc_stream *s)
     s->photo_pairs = s->photo_on ? s->pairs_submitted : 0;
     s->consist_pairs = s->consist_on ? s->pairs_submitted : 0;
     s->repair_pairs = s->repair_on ? s->pairs_submitted : 0;
+    s->traj_pairs = s->traj_P ? s->pairs_submitted : 0;
     s->pairs_submitted = 0;
 }
 
@@ -195,6 +205,7 @@ int submit(ofc_stream *s, int i)
     if (s->photo_on) OFC_TRY(room(s->photo_stats));
     if (s->consist_on) OFC_TRY(room(s->consist_counts));
     if (s->repair_on) OFC_TRY(room(s->repair_counts));
+    if (s->traj_P) OFC_TRY(room(s->traj_pos));
     OFC_HIP(hipMemcpyAsync(sl.frames.p, sl.pinned, P * sl.n_frames, hipMemcpyHostToDevice, s->copy));
     OFC_HIP(hipEventRecord(sl.uploaded, s->copy));
     OFC_HIP(hipStreamWaitEvent(s->compute, sl.uploaded, 0));
@@ -225,6 +236,17 @@ int submit(ofc_stream *s, int i)
         OFC_TRY(launch_repair(sl.flows.as<float>(), st, s->W, s->H, npair, s->repair_keep, s->repair_radius, s->repair_rounds,
                               s->repair_min_count, s->repair_smooth != 0, sl.flows.as<float>(), nullptr, st,
                               s->repair_counts.row<int64_t>(base), rs, s->compute));
+    }
+    // the points land by the whole, repaired flow (the rule of the moves): placed at the clip's first pair, carried by the
+    // table's last row afterwards
+    if (s->traj_P) {
+        OFC_REQUIRE(!s->traj_use_state || check_state, "the trajectories use the state map of a check the stream no longer has");
+        int32_t *len = s->traj_len.as<int32_t>();
+        uint8_t *why = s->traj_why.as<uint8_t>();
+        const int32_t *from = base > 0 ? s->traj_pos.row<int32_t>(base - 1) : s->traj_seeds.as<int32_t>();
+        if (base == 0) OFC_TRY(launch_traj_begin(from, s->traj_P, const_cast<int32_t *>(from), len, why, s->compute));
+        OFC_TRY(launch_traj_steps(sl.flows.as<float>(), s->traj_use_state ? check_state : nullptr, s->W, s->H, base, npair, s->traj_P,
+                                  check_keep, from, s->traj_pos.row<int32_t>(base), len, why, s->compute));
     }
     // where the pixels go is what the whole flow says: the moves are taken before the camera is subtracted
     if (s->link_max) OFC_TRY(launch_blob_moves(sl.flows.as<float>(), s->W, s->H, npair, s->link_moves.as<int32_t>(), s->compute));
@@ -712,6 +734,55 @@ int ofc_stream_read_repair(ofc_stream_t *s, int64_t *counts_host, int max_pairs)
     OFC_REQUIRE(counts_host, "null pointer");
     // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
     OFC_HIP(hipMemcpy(counts_host, s->repair_counts.buf.p, s->repair_counts.per * (size_t)s->repair_pairs, hipMemcpyDeviceToHost));
+    return OFC_OK;
+}
+
+int ofc_stream_set_traj(ofc_stream_t *s, int64_t P, const int32_t *seeds_host, int use_state)
+{
+    OFC_REQUIRE(s, "null pointer");
+    if (P != 0) {
+        OFC_TRY(traj_check(s->W, s->H, s->batch, P, 0, 0));
+        OFC_REQUIRE(seeds_host, "null pointer");
+        OFC_REQUIRE(!use_state || s->photo_on || s->consist_on,
+                    "use_state needs the state map of a check (ofc_stream_set_photo or ofc_stream_set_consist)");
+    }
+    OFC_TRY(require_idle(s, "set the trajectories on a fresh stream or straight after a finish"));
+    OFC_TRY(ensure_device(s->device));
+    s->traj_pairs = 0;
+    s->traj_pos.reset(sizeof(int32_t) * 2 * (size_t)P);      // the table's layout may change: it is empty, start over
+    if (P == 0) {
+        s->traj_seeds.release();
+        s->traj_len.release();
+        s->traj_why.release();
+        s->traj_P = 0;
+        s->traj_use_state = false;
+        return OFC_OK;
+    }
+    s->traj_P = 0;                                           // a failed allocation leaves the stage off
+    OFC_TRY(s->traj_seeds.alloc(sizeof(int32_t) * 2 * (size_t)P));
+    OFC_TRY(s->traj_len.alloc(sizeof(int32_t) * (size_t)P));
+    OFC_TRY(s->traj_why.alloc((size_t)P));
+    OFC_HIP(hipMemcpy(s->traj_seeds.p, seeds_host, sizeof(int32_t) * 2 * (size_t)P, hipMemcpyHostToDevice));
+    s->traj_P = P;
+    s->traj_use_state = use_state != 0;
+    return OFC_OK;
+}
+
+int ofc_stream_read_traj(ofc_stream_t *s, int32_t *pos_host, int32_t *len_host, uint8_t *why_host, int max_pairs)
+{
+    OFC_REQUIRE(s, "null pointer");
+    OFC_REQUIRE(s->traj_P > 0, "the stream has no trajectories (ofc_stream_set_traj)");
+    OFC_TRY(require_idle(s, "read the trajectories straight after a finish"));
+    OFC_REQUIRE(max_pairs >= s->traj_pairs, "the outputs hold %d pairs, the last finish delivered %d", max_pairs, s->traj_pairs);
+    OFC_TRY(ensure_device(s->device));
+    if (!s->traj_pairs) return OFC_OK;
+    OFC_REQUIRE(pos_host && len_host && why_host, "null pointer");
+    // nothing of this stream is in flight (checked above; a finish has waited for the compute stream)
+    const size_t P = (size_t)s->traj_P, row = sizeof(int32_t) * 2 * P;
+    OFC_HIP(hipMemcpy(pos_host, s->traj_seeds.p, row, hipMemcpyDeviceToHost));
+    OFC_HIP(hipMemcpy(pos_host + 2 * P, s->traj_pos.buf.p, row * (size_t)s->traj_pairs, hipMemcpyDeviceToHost));
+    OFC_HIP(hipMemcpy(len_host, s->traj_len.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+    OFC_HIP(hipMemcpy(why_host, s->traj_why.p, P, hipMemcpyDeviceToHost));
     return OFC_OK;
 }
 

@@ -41,6 +41,9 @@ every pixel that failed it, and the --blobs key map keeps only those that passed
 two constants (the literature's 0.01 and 0.5 px^2 by default, not tuned here); --fb-counts writes the (pairs, 4) pixel
 counts per state.
 
+With --trajectories FILE.npz a grid of points (--traj-step px apart) is followed through the clip's fields (trajectories.py),
+behind the repair and before the camera is removed, on the resident route, on --stream and on --fit-stream; pos, length and
+why go to FILE.npz.
 With --photometric every vector is put to the photometric check instead (photometric.py): the next frame, read where the
 pixel lands, must show the pixel's own grey value to within --photo-tau grey levels plus --photo-kappa times the local
 contrast (8 and 0.5 by default, a convention that is not tuned here).  It needs no second flow, so it works on the resident
@@ -198,7 +201,16 @@ def parse_arguments(argv=None):
                          "ROUNDS rounds (default 8, a convention, not tuned); any route")
     ap.add_argument("--repair-smooth", action="store_true", help="a median pass over the whole field behind the fill")
     ap.add_argument("--repair-counts", metavar="FILE.npy", help="write the (pairs, 3) counts of the repair to this .npy file")
+    ap.add_argument("--trajectories", metavar="FILE.npz",
+                    help="follow a grid of points through the clip's (repaired) fields and write pos, length and why to this "
+                         ".npz file (any route)")
+    ap.add_argument("--traj-step", type=float, default=8.0, help="spacing of the seed grid in px (default 8)")
     args = ap.parse_args(argv)
+    if not (np.isfinite(args.traj_step) and args.traj_step > 0):
+        ap.error("--traj-step must be a positive number of pixels")
+    if args.traj_step != 8.0 and not args.trajectories:
+        ap.error("--traj-step belongs to --trajectories")
+    args.traj_spec = dict(step=args.traj_step) if args.trajectories else None
     args.repair_spec = None
     if args.repair:
         try:
@@ -300,6 +312,16 @@ def _save_npy(path, a):
     np.save(path, a)
 
 
+def _save_trajectories(path, tr):
+    """pos (pairs+1, P, 2) int32 in 1/65536 px, length (P,) int32 and why (P,) u8 as one .npz archive under exactly this name"""
+    from .trajectories import WHY_NAMES
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as f:
+        np.savez(f, pos=tr.pos, length=tr.length, why=tr.why)
+    ends = np.bincount(tr.why, minlength=4)
+    print(f"trajectories: {len(tr)} points over {tr.n_pairs} pairs, " + ", ".join(f"{int(c)} {name}" for name, c in zip(WHY_NAMES, ends)))
+
+
 def _print_repair(counts):
     total = max(int(counts.sum()), 1)
     print("repair: " + ", ".join(f"{100.0 * c / total:.2f} % {name}" for name, c in zip(("sources", "filled", "unfilled"), counts.sum(0))))
@@ -314,11 +336,11 @@ def _print_photometric(stats, tau_q, kappa_q):
 
 
 def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=None, camera_out=None, blobs=None, blobs_out=None,
-                  max_links=0, photometric=None, photo_out=None, repair=None, repair_out=None):
+                  max_links=0, photometric=None, photo_out=None, repair=None, repair_out=None, trajectories=None, traj_out=None):
     """the (pairs, cells, k) counts of a model on a clip that is read frame by frame and never resident; camera as
     FlowStream's, its (pairs, 6) models saved to camera_out; blobs as FlowStream's, their rows written to blobs_out, with
     max_links linked and with their track ids; photometric as FlowStream's, its (pairs, 5) stats saved to photo_out; repair
-    as FlowStream's, its (pairs, 3) counts saved to repair_out"""
+    as FlowStream's, its (pairs, 3) counts saved to repair_out; trajectories as FlowStream's, saved to traj_out"""
     from .stream import FlowStream
     fs, n = None, 0
     if blobs is not None and max_links:
@@ -327,7 +349,8 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
         for gray in gray_frames(path, device):
             if fs is None:
                 fs = FlowStream(gray.shape[1], gray.shape[0], batch_pairs, rows, cols, device=device, centers=centers,
-                                camera=camera, blobs=blobs, photometric=photometric, repair=repair)
+                                camera=camera, blobs=blobs, photometric=photometric, repair=repair,
+                                trajectories=trajectories if traj_out else None)
             fs.push(gray)
             n += 1
         if n < 2:
@@ -347,6 +370,8 @@ def stream_counts(path, centers, rows, cols, batch_pairs=8, device=0, camera=Non
             _print_repair(filled)
             if repair_out:
                 _save_npy(repair_out, filled)
+        if trajectories is not None and traj_out:
+            _save_trajectories(traj_out, fs.trajectories())
         return counts
     finally:
         if fs is not None:
@@ -389,13 +414,13 @@ def main(argv=None):
                                  device=args.device)
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
                                args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts,
-                               args.repair_spec, args.repair_counts)
+                               args.repair_spec, args.repair_counts, args.traj_spec, args.trajectories)
         return _write_outputs(args, counts, centers)
     if args.stream:
         centers = given
         counts = stream_counts(args.path, centers, args.rows, args.cols, args.batch_pairs, args.device, args.camera_spec,
                                args.camera_out, args.blob_spec, args.blobs, args.max_links, args.photo_spec, args.photo_counts,
-                               args.repair_spec, args.repair_counts)
+                               args.repair_spec, args.repair_counts, args.traj_spec, args.trajectories)
         return _write_outputs(args, counts, centers)
     from .pipeline import ClipPipeline
     frames = read_gray_frames(args.path, args.device)
@@ -425,6 +450,8 @@ def main(argv=None):
             _print_repair(filled)
             if args.repair_counts:
                 _save_npy(args.repair_counts, filled)
+        if args.traj_spec:                      # a point lands by the whole flow: before the camera is taken out
+            _save_trajectories(args.trajectories, pipe.trajectories(**args.traj_spec))
         if args.camera_spec:
             if args.max_links:
                 pipe.capture_moves()            # where the pixels go: before the camera is taken out of the field

@@ -252,6 +252,28 @@ class ClipPipeline:
         self._label_k = None                # the labels belong to the field as it was
         return np.concatenate(counts)
 
+    def trajectories(self, seeds=None, step=8, start=0, length=None, consistent=False, keep=(0,), pairs_per_launch=0):
+        """follow points through the resident field (trajectories.py; ofc_traj_dev) -> trajectories.Trajectories.  seeds:
+        int32 (P,2) in 1/65536 px, None for trajectories.grid_seeds(W, H, step); the points are placed at pair `start` and
+        followed through `length` pairs (None: to the end of the clip): a sub-range is a pointer offset into the field.
+        consistent=True: a point ends where the state map that consistency() or photometric() left (and repair() updated)
+        is not in `keep`; ValueError without one.  ValueError after compensate_camera(): a residual does not say where a
+        pixel lands (the rule consistency() has), so follow before the camera is removed.  Rank-local: this rank's pairs."""
+        from . import trajectories as tr
+        if self._compensated:
+            raise ValueError("trajectories() after compensate_camera() would follow the residual, which does not say where a "
+                             "pixel lands: call it before compensate_camera()")
+        start = int(start)
+        n = self.n_pairs - start if length is None else int(length)
+        if not (0 <= start < self.n_pairs and 1 <= n <= self.n_pairs - start):
+            raise ValueError(f"start = {start}, length = {length!r}: a range of the clip's {self.n_pairs} pairs")
+        state_ptr = self._state_ptr("trajectories(consistent=True)") if consistent else None
+        self.sync()
+        P = self.W * self.H
+        return tr.follow_dev(self.flows.ptr + start * P * 8, self.W, self.H, n, tr._seeds(seeds, self.W, self.H, step),
+                             state_ptr=state_ptr + start * P if consistent else None, keep=keep, pairs_per_launch=pairs_per_launch,
+                             device=self.device)
+
     def filled_host(self):
         """host copy of repair()'s map: (n,H,W) u8, 0 for a source, g for a pixel filled in round g, 255 for one never filled"""
         if self.filled is None:

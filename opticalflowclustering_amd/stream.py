@@ -15,7 +15,9 @@ With a repair (repair=True or dict(radius=, rounds=, min_count=, smooth=, keep=)
 in by the median of their trusted neighbours before anything else looks at the field (repair.py): repair_stats().
 With a forward-backward check (consistency=True or dict(alpha=, beta=, keep=)) every batch's flow is computed in both
 directions from one front end and every pair's vectors are checked against the flow back (consistency.py):
-consistency_stats(); the repair and the blobs use its states as they use the photometric check's.  One check per stream."""
+consistency_stats(); the repair and the blobs use its states as they use the photometric check's.  One check per stream.
+With trajectories (trajectories=True or dict(step=, seeds=, use_state=)) points are followed through the clip's repaired
+fields, across batches (trajectories.py): trajectories() after a finish."""
 import ctypes as C
 
 import numpy as np
@@ -25,7 +27,7 @@ from ._lib import FbParams, check, load, ptr
 
 class FlowStream:
     def __init__(self, W, H, batch_pairs=8, rows=14, cols=25, params=None, device=0, centers=None, mean=None, sums=False,
-                 histogram=None, camera=None, blobs=None, photometric=None, repair=None, consistency=None):
+                 histogram=None, camera=None, blobs=None, photometric=None, repair=None, consistency=None, trajectories=None):
         self.W, self.H, self.rows, self.cols = W, H, rows, cols
         self.params = params or FbParams()
         h = C.c_void_p()
@@ -55,6 +57,35 @@ class FlowStream:
         self.repair_args = None             # (keep, radius, rounds, min_count, smooth) of the stream's repair, or None
         if repair is not None and repair is not False:
             self.set_repair(**({} if repair is True else repair))
+        self.traj_points = 0                # the points the stream follows, 0 without trajectories
+        if trajectories is not None and trajectories is not False:
+            self.set_trajectories(**({} if trajectories is True else trajectories))
+
+    def set_trajectories(self, step=8, seeds=None, use_state=False, on=True):
+        """from the next clip on, follow points through every pair's field (ofc_stream_set_traj; trajectories.py has the
+        definition): seeds int32 (P,2) in 1/65536 px, None for trajectories.grid_seeds(W, H, step).  The points are placed at
+        the first pair after this call or after a finish and carried across batches; the advection runs directly behind the
+        repair and before the moves and a camera, so a point lands by the whole flow.  use_state: a point ends where the state
+        map of the stream's check is not in that check's keep; ValueError without a check.  on=False removes the stage.
+        Only on a stream that holds no frame and no undelivered result, as set_model; ValueError otherwise."""
+        if not on:
+            check(load().ofc_stream_set_traj(self._h, 0, None, 0))
+            self.traj_points, self._last_pairs = 0, 0
+            return
+        from .trajectories import _seeds
+        s = _seeds(seeds, self.W, self.H, step)
+        check(load().ofc_stream_set_traj(self._h, len(s), ptr(s), int(bool(use_state))))
+        self.traj_points, self._last_pairs = len(s), 0
+
+    def trajectories(self):
+        """-> trajectories.Trajectories of the pairs the last finish() / finish_clusters() delivered (ofc_stream_read_traj); a
+        point whose why is RAN was still live when the clip ended.  Straight after a finish only; ValueError once frames
+        are held again, and on a stream without trajectories."""
+        from .trajectories import Trajectories
+        n, P = self._last_pairs, max(self.traj_points, 1)
+        pos, length, why = np.zeros((max(n, 1) + 1, P, 2), np.int32), np.zeros(P, np.int32), np.zeros(P, np.uint8)
+        check(load().ofc_stream_read_traj(self._h, ptr(pos), ptr(length), ptr(why), max(n, 1)))
+        return Trajectories(pos[:n + 1], length, why)
 
     def set_consistency(self, alpha=None, beta=None, keep=(0,), on=True):
         """from the next batch on, compute every batch's flow in both directions from one front end
