@@ -638,8 +638,7 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter_p(const float *__restrict_
 constexpr size_t FP_LDS = sizeof(double) * 5 * BS_ROWS * 272 + sizeof(float) * FP_NL * 5 * 256;
 
 int launch_flow_iter_pipe(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W,
-                          int H, int rows_per_block, hipStream_t s, double *uv_sum, double *uv_scratch,
-                          size_t uv_scratch_doubles)
+                          int H, const FlowIterGrid &g, hipStream_t s, const FlowSums &sums)
 {
     static bool attr_set = false;       // 79,360 B of dynamic LDS: above the 64 KB default
     if (!attr_set) {
@@ -647,17 +646,15 @@ int launch_flow_iter_pipe(const float *R, size_t frame_stride_R, const float *fl
         OFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_flow_iter_p<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FP_LDS));
         attr_set = true;
     }
-    const int tx = cdiv(W, 256 - 14), ns = cdiv(H, rows_per_block);
-    const int grid = cdiv(tx * ns, 8) * 8 * npair;
-    if (uv_sum) {
-        if ((size_t)grid * 2 > uv_scratch_doubles) { set_error("flow sums: scratch too small (%d work-groups)", grid); return OFC_EINVAL; }
-        hipLaunchKernelGGL((k_flow_iter_p<true>), dim3(grid), dim3(256), FP_LDS, s, R, frame_stride_R, flow_in, flow_out, W, H,
-                           rows_per_block, tx, ns, npair, uv_scratch);
+    if (sums.out) {
+        if ((size_t)g.grid * 2 > sums.doubles) { set_error("flow sums: scratch too small (%d work-groups)", g.grid); return OFC_EINVAL; }
+        hipLaunchKernelGGL((k_flow_iter_p<true>), dim3(g.grid), dim3(256), FP_LDS, s, R, frame_stride_R, flow_in, flow_out, W, H,
+                           g.rows, g.tiles_x, g.strips, npair, sums.scratch);
         OFC_HIP(hipGetLastError());
-        return launch_reduce_records(uv_scratch, grid, 2, uv_sum, s, nullptr);
+        return launch_reduce_records(sums.scratch, g.grid, 2, sums.out, s, nullptr);
     }
-    hipLaunchKernelGGL((k_flow_iter_p<false>), dim3(grid), dim3(256), FP_LDS, s, R, frame_stride_R, flow_in, flow_out, W, H,
-                       rows_per_block, tx, ns, npair, nullptr);
+    hipLaunchKernelGGL((k_flow_iter_p<false>), dim3(g.grid), dim3(256), FP_LDS, s, R, frame_stride_R, flow_in, flow_out, W, H,
+                       g.rows, g.tiles_x, g.strips, npair, nullptr);
     OFC_HIP(hipGetLastError());
     return OFC_OK;
 }

@@ -1819,7 +1819,7 @@ __global__ __launch_bounds__(256, 2) void k_flow_iter(const float *__restrict__ 
     }
 }
 
-int flow_iter_rows(int W, int H, int npair, int winsize)
+static int flow_iter_rows(int W, int H, int npair, int winsize)
 {
     // cost model: a launch runs in ceil(blocks / resident) rounds (224 VGPRs -> 2 work-groups per CU), each as
     // long as one strip incl. its 2m-row window warm-up.  Pick the strip count that minimises rounds x strip.
@@ -1839,11 +1839,22 @@ int flow_iter_rows(int W, int H, int npair, int winsize)
     return best_rows;
 }
 
-int flow_iter_max_grid(int W, int H, int npair, int winsize)
+// The one rule for the fused iteration's grid: every launch of k_flow_iter (and of its pipelined copy), the scratch its
+// column sums are written into and the geometry exports ask it.  A tile is 256 columns less the window's halo; the tiles of a
+// field are rounded up to groups of eight (one per XCD; the padding work-groups return at once).
+FlowIterGrid flow_iter_grid(int W, int H, int fields, int winsize, int rows)
 {
-    const int rows = flow_iter_rows(W, H, npair, winsize);
-    return cdiv(cdiv(W, 256 - (winsize - 1)) * cdiv(H, rows), 8) * 8 * npair;
+    FlowIterGrid g;
+    // a height of the caller's (the parity tests walk every strip height on small frames) is rounded up to whole
+    // super-steps, as the kernel needs; one above the frame is one strip
+    g.rows = rows == 0 ? flow_iter_rows(W, H, fields, winsize) : cdiv(std::min(rows, 1 << 30), 16) * 16;
+    g.tiles_x = cdiv(W, 256 - (winsize - 1));
+    g.strips = cdiv(H, g.rows);
+    g.grid = cdiv(g.tiles_x * g.strips, 8) * 8 * fields;
+    return g;
 }
+
+int flow_iter_max_grid(int W, int H, int npair, int winsize) { return flow_iter_grid(W, H, npair, winsize).grid; }
 
 // the limits of launch_flow_iter that depend on the level's size and the window alone (also asked by flow_levels_check)
 static int flow_iter_check(int W, int H, int winsize)
@@ -1853,131 +1864,111 @@ static int flow_iter_check(int W, int H, int winsize)
     return OFC_OK;
 }
 
-int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out,
-                     int npair, int W, int H, int winsize, hipStream_t s, const float *coarse, int sw, int sh,
-                     float mul, double *uv_sum, double *uv_scratch, size_t uv_scratch_doubles, int rows_per_block)
+static UpsArgs ups_args(const FlowCoarse &c, int W, int H)
 {
-    OFC_TRY(flow_iter_check(W, H, winsize));
-    if (rows_per_block < 0) { set_error("rows_per_block %d is negative (0 = automatic)", rows_per_block); return OFC_EINVAL; }
-    // a height of the caller's (the parity tests walk every strip height on small frames) is rounded up to whole
-    // super-steps, as the kernel needs; one above the frame is one strip
-    if (rows_per_block == 0) rows_per_block = flow_iter_rows(W, H, npair, winsize);
-    else rows_per_block = cdiv(std::min(rows_per_block, 1 << 30), 16) * 16;
     UpsArgs u;
-    u.src = coarse; u.sw = sw; u.sh = sh; u.mul = mul;
-    u.scx = coarse ? (double)sw / W : 1.0; u.scy = coarse ? (double)sh / H : 1.0;
-    // OFC_FLOW_PIPE=1: the software-pipelined experiment of flow_experiments.hip (bit-identical output, 2.6x slower: it
-    // does not fit 256 VGPRs); read at every launch because its parity test toggles it
-    {
-        const char *e = getenv("OFC_FLOW_PIPE");
-        if (e && e[0] == '1' && winsize == 15 && !coarse)
-            return launch_flow_iter_pipe(R, frame_stride_R, flow_in, flow_out, npair, W, H, rows_per_block, s, uv_sum, uv_scratch,
-                                         uv_scratch_doubles);
-    }
-    if (uv_sum) {               // the last iteration of level 0: also sum(u), sum(v) of the field it writes -> uv_sum[2]
-        if (coarse || winsize != 15) { set_error("flow sums are emitted by the plain winsize-15 iteration only"); return OFC_EUNSUPPORTED; }
-        const int tx = cdiv(W, 256 - 14), ns = cdiv(H, rows_per_block);
-        const int grid = cdiv(tx * ns, 8) * 8 * npair;
-        if ((size_t)grid * 2 > uv_scratch_doubles) { set_error("flow sums: scratch too small (%d work-groups)", grid); return OFC_EINVAL; }
-        hipLaunchKernelGGL((k_flow_iter<7, 0, false, true>), dim3(grid), dim3(256), 0, s, R, frame_stride_R, flow_in, flow_out, W, H,
-                           rows_per_block, u, tx, ns, npair, nullptr, uv_scratch);
-        OFC_HIP(hipGetLastError());
-        return launch_reduce_records(uv_scratch, grid, 2, uv_sum, s, nullptr);
-    }
-    dim3 block(256);
-#define OFC_FI_CASE(MM)                                                                                  \
-    case 2 * MM + 1: {                                                                                   \
-        const int tx = cdiv(W, 256 - 2 * MM), ns = cdiv(H, rows_per_block);                              \
-        dim3 grid(cdiv(tx * ns, 8) * 8 * npair);                                                         \
-        if (coarse && u.scx == 0.5 && u.scy == 0.5)                                                      \
-            hipLaunchKernelGGL((k_flow_iter<MM, 2>), grid, block, 0, s, R, frame_stride_R, flow_in,      \
-                               flow_out, W, H, rows_per_block, u, tx, ns, npair);                        \
-        else if (coarse)                                                                                 \
-            hipLaunchKernelGGL((k_flow_iter<MM, 1>), grid, block, 0, s, R, frame_stride_R, flow_in,      \
-                               flow_out, W, H, rows_per_block, u, tx, ns, npair);                        \
-        else                                                                                             \
-            hipLaunchKernelGGL((k_flow_iter<MM, 0>), grid, block, 0, s, R, frame_stride_R, flow_in,      \
-                               flow_out, W, H, rows_per_block, u, tx, ns, npair);                        \
-        break;                                                                                           \
-    }
+    u.src = c.src; u.sw = c.sw; u.sh = c.sh; u.mul = c.mul;
+    u.scx = c.src ? (double)c.sw / W : 1.0; u.scy = c.src ? (double)c.sh / H : 1.0;
+    return u;
+}
+
+// what every build of k_flow_iter takes besides its grid; p12 and p13 are the kernel's last two pointers (null in the
+// forward form, the bases of the backward halves in the bidirectional one)
+struct FlowIterArgs {
+    const float *R;
+    size_t frame_stride_R;
+    const float *flow_in;
+    float *flow_out;
+    int W, H, fields;
+    UpsArgs u;
+    unsigned long long *p12;
+    double *p13;
+};
+
+template <int MM, int UPS, bool BIDIR>
+static void flow_iter_launch(const FlowIterGrid &g, const FlowIterArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_flow_iter<MM, UPS, false, false, BIDIR>), dim3(g.grid), dim3(256), 0, s, a.R, a.frame_stride_R, a.flow_in,
+                       a.flow_out, a.W, a.H, g.rows, a.u, g.tiles_x, g.strips, a.fields, a.p12, a.p13);
+}
+
+// the window picks MM; the coarse level picks UPS: 2 for the exact x2 pyramid, 1 for general taps, 0 for none
+template <int MM, bool BIDIR>
+static void flow_iter_launch_ups(const FlowIterGrid &g, const FlowIterArgs &a, hipStream_t s)
+{
+    if (a.u.src && a.u.scx == 0.5 && a.u.scy == 0.5) flow_iter_launch<MM, 2, BIDIR>(g, a, s);
+    else if (a.u.src) flow_iter_launch<MM, 1, BIDIR>(g, a, s);
+    else flow_iter_launch<MM, 0, BIDIR>(g, a, s);
+}
+
+template <bool BIDIR>
+static int flow_iter_dispatch(int winsize, const FlowIterGrid &g, const FlowIterArgs &a, hipStream_t s)
+{
     switch (winsize) {
-        OFC_FI_CASE(2)
-        OFC_FI_CASE(3)
-        OFC_FI_CASE(4)
-        OFC_FI_CASE(5)
-        OFC_FI_CASE(6)
-        OFC_FI_CASE(7)
+    case 5: flow_iter_launch_ups<2, BIDIR>(g, a, s); break;
+    case 7: flow_iter_launch_ups<3, BIDIR>(g, a, s); break;
+    case 9: flow_iter_launch_ups<4, BIDIR>(g, a, s); break;
+    case 11: flow_iter_launch_ups<5, BIDIR>(g, a, s); break;
+    case 13: flow_iter_launch_ups<6, BIDIR>(g, a, s); break;
+    case 15: flow_iter_launch_ups<7, BIDIR>(g, a, s); break;
     default:
         set_error("winsize %d unsupported by the fused iteration (odd 5..15)", winsize);
         return OFC_EUNSUPPORTED;
     }
-#undef OFC_FI_CASE
     OFC_HIP(hipGetLastError());
     return OFC_OK;
 }
 
+int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W, int H,
+                     int winsize, hipStream_t s, const FlowCoarse &coarse, const FlowSums &sums, int rows_per_block)
+{
+    OFC_TRY(flow_iter_check(W, H, winsize));
+    if (rows_per_block < 0) { set_error("rows_per_block %d is negative (0 = automatic)", rows_per_block); return OFC_EINVAL; }
+    const FlowIterGrid g = flow_iter_grid(W, H, npair, winsize, rows_per_block);
+    // OFC_FLOW_PIPE=1: the software-pipelined experiment of flow_experiments.hip (bit-identical output, 2.6x slower: it
+    // does not fit 256 VGPRs); read at every launch because its parity test toggles it
+    {
+        const char *e = getenv("OFC_FLOW_PIPE");
+        if (e && e[0] == '1' && winsize == 15 && !coarse.src) return launch_flow_iter_pipe(R, frame_stride_R, flow_in, flow_out, npair, W, H, g, s, sums);
+    }
+    const FlowIterArgs a = {R, frame_stride_R, flow_in, flow_out, W, H, npair, ups_args(coarse, W, H), nullptr, nullptr};
+    if (sums.out) {             // the last iteration of level 0: also sum(u), sum(v) of the field it writes -> sums.out[2]
+        if (coarse.src || winsize != 15) { set_error("flow sums are emitted by the plain winsize-15 iteration only"); return OFC_EUNSUPPORTED; }
+        if ((size_t)g.grid * 2 > sums.doubles) { set_error("flow sums: scratch too small (%d work-groups)", g.grid); return OFC_EINVAL; }
+        hipLaunchKernelGGL((k_flow_iter<7, 0, false, true>), dim3(g.grid), dim3(256), 0, s, R, frame_stride_R, flow_in, flow_out, W, H,
+                           g.rows, a.u, g.tiles_x, g.strips, npair, nullptr, sums.scratch);
+        OFC_HIP(hipGetLastError());
+        return launch_reduce_records(sums.scratch, g.grid, 2, sums.out, s, nullptr);
+    }
+    return flow_iter_dispatch<false>(winsize, g, a, s);
+}
+
 // One iteration of both directions of `npair` frame pairs (k_flow_iter<.., BIDIR>): 2 npair logical pairs in one grid, strips
-// sized for that work.  in/out/coarse: the forward and the backward half of each buffer, [npair] fields each; coarse_* null =
-// in_* is at this level's size.
+// sized for that work.  in/out/coarse: the forward and the backward half of each buffer, [npair] fields each; coarse.src null
+// = in_* is at this level's size.
 int launch_flow_iter_bidir(const float *R, size_t frame_stride_R, const float *in_fwd, const float *in_bwd, float *out_fwd,
-                           float *out_bwd, int npair, int W, int H, int winsize, hipStream_t s, const float *coarse_fwd,
-                           const float *coarse_bwd, int sw, int sh, float mul)
+                           float *out_bwd, int npair, int W, int H, int winsize, hipStream_t s, const FlowCoarse &coarse,
+                           const float *coarse_bwd)
 {
     OFC_TRY(flow_iter_check(W, H, winsize));
     if (npair < 1 || npair > (1 << 20)) { set_error("bidirectional iteration: %d pairs", npair); return OFC_EINVAL; }
     const int lp = 2 * npair;
-    const int rows_per_block = flow_iter_rows(W, H, lp, winsize);
-    UpsArgs u;
-    u.src = coarse_fwd; u.sw = sw; u.sh = sh; u.mul = mul;
-    u.scx = coarse_fwd ? (double)sw / W : 1.0; u.scy = coarse_fwd ? (double)sh / H : 1.0;
     // the backward bases ride in the two pointer arguments the forward form leaves unused (see k_flow_iter)
     unsigned long long *out_b = reinterpret_cast<unsigned long long *>(out_bwd);
-    double *in_b = reinterpret_cast<double *>(const_cast<float *>(coarse_fwd ? coarse_bwd : in_bwd));
-    dim3 block(256);
-#define OFC_FI_CASE(MM)                                                                                  \
-    case 2 * MM + 1: {                                                                                   \
-        const int tx = cdiv(W, 256 - 2 * MM), ns = cdiv(H, rows_per_block);                              \
-        dim3 grid(cdiv(tx * ns, 8) * 8 * lp);                                                            \
-        if (coarse_fwd && u.scx == 0.5 && u.scy == 0.5)                                                  \
-            hipLaunchKernelGGL((k_flow_iter<MM, 2, false, false, true>), grid, block, 0, s, R, frame_stride_R, in_fwd, \
-                               out_fwd, W, H, rows_per_block, u, tx, ns, lp, out_b, in_b);               \
-        else if (coarse_fwd)                                                                             \
-            hipLaunchKernelGGL((k_flow_iter<MM, 1, false, false, true>), grid, block, 0, s, R, frame_stride_R, in_fwd, \
-                               out_fwd, W, H, rows_per_block, u, tx, ns, lp, out_b, in_b);               \
-        else                                                                                             \
-            hipLaunchKernelGGL((k_flow_iter<MM, 0, false, false, true>), grid, block, 0, s, R, frame_stride_R, in_fwd, \
-                               out_fwd, W, H, rows_per_block, u, tx, ns, lp, out_b, in_b);               \
-        break;                                                                                           \
-    }
-    switch (winsize) {
-        OFC_FI_CASE(2)
-        OFC_FI_CASE(3)
-        OFC_FI_CASE(4)
-        OFC_FI_CASE(5)
-        OFC_FI_CASE(6)
-        OFC_FI_CASE(7)
-    default:
-        set_error("winsize %d unsupported by the fused iteration (odd 5..15)", winsize);
-        return OFC_EUNSUPPORTED;
-    }
-#undef OFC_FI_CASE
-    OFC_HIP(hipGetLastError());
-    return OFC_OK;
+    double *in_b = reinterpret_cast<double *>(const_cast<float *>(coarse.src ? coarse_bwd : in_bwd));
+    const FlowIterArgs a = {R, frame_stride_R, in_fwd, out_fwd, W, H, lp, ups_args(coarse, W, H), out_b, in_b};
+    return flow_iter_dispatch<true>(winsize, flow_iter_grid(W, H, lp, winsize), a, s);
 }
 
 // diagnostic launch of the stamped build (non-UPS, winsize 15); dbg: [grid][4][8] u64, zeroed by the caller
 int launch_flow_iter_stamped(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W,
                              int H, hipStream_t s, unsigned long long *dbg, int *grid_out)
 {
-    const int rows_per_block = flow_iter_rows(W, H, npair, 15);
-    UpsArgs u;
-    u.src = nullptr; u.sw = 0; u.sh = 0; u.mul = 1.f; u.scx = 1.0; u.scy = 1.0;
-    const int tx = cdiv(W, 256 - 14), ns = cdiv(H, rows_per_block);
-    dim3 grid(cdiv(tx * ns, 8) * 8 * npair);
-    if (grid_out) *grid_out = (int)grid.x;
+    const FlowIterGrid g = flow_iter_grid(W, H, npair, 15);
+    if (grid_out) *grid_out = g.grid;
     if (dbg)
-        hipLaunchKernelGGL((k_flow_iter<7, 0, true>), grid, dim3(256), 0, s, R, frame_stride_R, flow_in, flow_out, W, H,
-                           rows_per_block, u, tx, ns, npair, dbg);
+        hipLaunchKernelGGL((k_flow_iter<7, 0, true>), dim3(g.grid), dim3(256), 0, s, R, frame_stride_R, flow_in, flow_out, W, H,
+                           g.rows, ups_args(FlowCoarse(), W, H), g.tiles_x, g.strips, npair, dbg);
     OFC_HIP(hipGetLastError());
     return OFC_OK;
 }

@@ -82,6 +82,9 @@ struct PolyConsts {
     double ig11, ig03, ig33, ig55;
 };
 void polyexp_setup(int n, double sigma, PolyConsts &c);        // FarnebackPrepareGaussian
+// the frame size and the Farneback parameters every flow entry point accepts: OFC_OK, or OFC_EINVAL / OFC_EUNSUPPORTED with the
+// message set (an odd winsize above OFC_WINSIZE_MAX is refused here, an even one where a window is used)
+int check_frame_and_fb_params(const ofc_fb_params &p, int W, int H);
 int polyexp_n_check(int n);        // OFC_OK for the built poly_n (5, 7), else OFC_EUNSUPPORTED with the message set
 constexpr int WINSIZE_WIDE_MIN = 19;   // launch_box_solve: this winsize and wider run k_box_solve_wide (up to OFC_WINSIZE_MAX)
 
@@ -109,22 +112,36 @@ int launch_box_solve(const float *M, float *flow, int npair, int W, int H, int w
 // src [npair][sh][sw][2] -> dst [npair][dh][dw][2], * mul
 int launch_flow_resize(const float *src, float *dst, int npair, int sw, int sh, int dw, int dh,
                        float mul, hipStream_t s);
+// launch geometry of the fused iteration over `fields` flow fields of a W x H level: strips `rows` high (a multiple of 16),
+// tiles_x column tiles of 256 - (winsize - 1) columns, `grid` work-groups (the tiles of a field rounded up to groups of eight).
+// rows 0: the height the kernel's cost model picks for this size and batch; a caller's height is rounded up to a multiple of 16
+struct FlowIterGrid {
+    int rows, tiles_x, strips, grid;
+};
+FlowIterGrid flow_iter_grid(int W, int H, int fields, int winsize, int rows = 0);
+// the coarser level a level's first iteration starts from: the initial flow is resize(src [npair][sh][sw][2], (W,H)) * mul,
+// sampled on the fly.  src null: flow_in is at this level's size
+struct FlowCoarse {
+    const float *src = nullptr;
+    int sw = 0, sh = 0;
+    float mul = 1.f;
+};
+// the column sums of the field an iteration writes: sum(u), sum(v) -> out[2], through `scratch` of `doubles` doubles (two per
+// work-group; too few is OFC_EINVAL).  out null: none
+struct FlowSums {
+    double *out = nullptr, *scratch = nullptr;
+    size_t doubles = 0;
+};
 // fused iteration (update matrices + box mean + solve): R [npair+1][5][H][W]; flow_in != flow_out
-// coarse != nullptr: the initial flow is resize(coarse [npair][sh][sw][2], (W,H)) * mul, sampled on the fly
-// rows_per_block: strip height, rounded up to a multiple of 16; 0 = flow_iter_rows (what the engine passes); < 0 OFC_EINVAL
-int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out,
-                     int npair, int W, int H, int winsize, hipStream_t s, const float *coarse = nullptr,
-                     int sw = 0, int sh = 0, float mul = 1.f, double *uv_sum = nullptr, double *uv_scratch = nullptr,
-                     size_t uv_scratch_doubles = 0, int rows_per_block = 0);
+// rows_per_block: strip height as flow_iter_grid takes it (0 is what the engine passes); < 0 OFC_EINVAL
+int launch_flow_iter(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W, int H,
+                     int winsize, hipStream_t s, const FlowCoarse &coarse = {}, const FlowSums &sums = {}, int rows_per_block = 0);
 // one iteration of both directions of npair frame pairs in one launch; every buffer comes as its forward and its backward
-// half ([npair] fields each, anywhere); strips are flow_iter_rows(W, H, 2 npair, winsize) high
+// half ([npair] fields each, anywhere; coarse_bwd goes with coarse.src); strips are flow_iter_grid(W, H, 2 npair, winsize) high
 int launch_flow_iter_bidir(const float *R, size_t frame_stride_R, const float *in_fwd, const float *in_bwd, float *out_fwd,
-                           float *out_bwd, int npair, int W, int H, int winsize, hipStream_t s,
-                           const float *coarse_fwd = nullptr, const float *coarse_bwd = nullptr, int sw = 0, int sh = 0,
-                           float mul = 1.f);
-// strip height the cost model of the fused iteration picks for a level of this size and batch (a multiple of 16)
-int flow_iter_rows(int W, int H, int npair, int winsize);
-// upper bound of the iteration kernel's grid (work-groups) for a level of this size at that height: sizes the uv_scratch above
+                           float *out_bwd, int npair, int W, int H, int winsize, hipStream_t s, const FlowCoarse &coarse = {},
+                           const float *coarse_bwd = nullptr);
+// the most work-groups launch_flow_iter starts for a level of this size at the model's height: sizes FlowSums::scratch
 int flow_iter_max_grid(int W, int H, int npair, int winsize);
 // two fused iterations flow_in -> flow_out (winsize 15; flow_in at this level's size, != flow_out); rows_per_block 0 = auto
 int launch_flow_iter2(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W,
@@ -134,8 +151,7 @@ int launch_flow_iter_w3(const float *R, size_t frame_stride_R, const float *flow
                         int H, int winsize, hipStream_t s, int rows_per_block = 0);
 // round-3 experiment (flow_experiments.hip): k_flow_iter with the next step's gathers issued across the exchange (winsize 15)
 int launch_flow_iter_pipe(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W,
-                          int H, int rows_per_block, hipStream_t s, double *uv_sum, double *uv_scratch,
-                          size_t uv_scratch_doubles);
+                          int H, const FlowIterGrid &g, hipStream_t s, const FlowSums &sums);
 int launch_flow_iter_stamped(const float *R, size_t frame_stride_R, const float *flow_in, float *flow_out, int npair, int W,
                              int H, hipStream_t s, unsigned long long *dbg, int *grid_out);
 // every size- and parameter-dependent limit of the launches above, for all levels of an engine (geom[0..levels]), with no

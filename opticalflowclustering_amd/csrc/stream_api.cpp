@@ -294,7 +294,7 @@ int submit(ofc_stream *s, int i)
 
 extern "C" {
 
-hipStream_t ofc_flow_stream_internal(ofc_flow_t *f);   // ofc_api.cpp
+hipStream_t ofc_flow_stream_internal(ofc_flow_t *f);   // flow_engine.cpp
 
 int ofc_stream_create(int device, int W, int H, const ofc_fb_params *p, int batch_pairs, int rows, int cols,
                       ofc_stream_t **out)

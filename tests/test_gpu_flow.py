@@ -402,6 +402,25 @@ def test_three_wave_iteration_kernel_equals_the_two_wave_one(st, W, H, rows):
     assert (d == 0).mean() >= 0.999
 
 
+def test_engine_with_three_wave_kernel_against_oracle_and_its_sums(monkeypatch):
+    """OFC_FLOW_W3=1 through the engine (the kernel alone is compared with k_flow_iter above): every iteration that does not
+    start from the coarser level runs k_flow_iter_w3, so no launch can carry the column sums and the sweep over the finished
+    field provides them.  The field meets the end-to-end bars against the oracle; the sums are the float64 sums of the
+    stored field to 1e-9 * max(1, |want|) (bar 4 of test_gpu_flow_sequences.py)."""
+    import flow_iter_sched_cases as K
+    name = "250x190"
+    monkeypatch.setenv("OFC_FLOW_W3", "1")
+    flows, uv = K.run(name, sums=True)
+    fr = K.frames(name)
+    want = O.farneback(fr[0], fr[1])
+    r, mx = rel(flows[0], want), np.abs(flows[0] - want).max()
+    print(f"w3 engine {name}: rel {r:.3e} max {mx:.3e}")
+    assert r <= K.REL_BAR and mx <= K.MAX_BAR, (r, mx)
+    sums = flows.astype(np.float64).reshape(-1, 2).sum(0)
+    print("sums", uv, "numpy", sums)
+    assert np.all(np.abs(uv - sums) <= 1e-9 * np.maximum(1.0, np.abs(sums))), (uv, sums)
+
+
 @pytest.mark.parametrize("W,H", [(480, 270), (700, 96), (243, 40), (1000, 300), (64, 16)])
 def test_pipelined_iteration_experiment_is_bit_identical(st, W, H, monkeypatch):
     """k_flow_iter_p (round 3, OFC_FLOW_PIPE=1: the next step's gathers issued across the exchange, 7 ring slots in LDS):

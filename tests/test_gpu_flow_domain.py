@@ -138,8 +138,8 @@ def _create(W, H, max_batch=1, **kw):
 
 EINVAL, EUNSUPPORTED, OK = -1, -6, 0        # include/ofc.h
 
-# (id, W, H, max_batch, parameters, code): every clause of check_params and ofc_flow_create, the value just outside and
-# the value just inside.  The 16384 side is tested through refusals only (no 16384^2 engine is allocated).
+# (id, W, H, max_batch, parameters, code): every clause of check_frame_and_fb_params and ofc_flow_create, the value just
+# outside and the value just inside.  The 16384 side is tested through refusals only (no 16384^2 engine is allocated).
 EDGE = [("W15", 15, 64, 1, {}, EINVAL), ("H15", 64, 15, 1, {}, EINVAL), ("16x16", 16, 16, 1, {}, OK),
         ("W16385", 16385, 64, 1, {}, EINVAL), ("H16385", 64, 16385, 1, {}, EINVAL),
         ("pyr_scale0", 64, 64, 1, dict(pyr_scale=0.0), EINVAL), ("pyr_scale1", 64, 64, 1, dict(pyr_scale=1.0), EINVAL),
