@@ -14,14 +14,30 @@ Observed on the MI355X, on the reference over the engine's pairwise fields of cl
     blobs                                      3    3    3    3    3    3    4    3    3
     links per transition                         5    4    4    4    5    6    6    4
     camera tx -1.94 .. -1.98, ty -0.99 .. -1.03 (the pan is (2, 1)); the repair changes 4802 move words and all 54 camera
-    parameters of the clip; 13317 pixels are background under the check's states and foreground under the repaired ones."""
+    parameters of the clip; 13317 pixels are background under the check's states and foreground under the repaired ones.
+
+With the forward-backward check (`consistency`, which needs `back`, the fields of the pairs taken backwards) in the photometric
+one's place and the trajectories behind the repair, the chain is ALL_FB, its wrong chains WRONG_FB; both steps are the integer
+CPU models of consistency_cases and trajectory_cases.  test_gpu_stream_compose_bidir.py holds FlowStream to it.
+
+Observed on the MI355X, on the reference of ALL_FB over the engine's pairwise fields of both directions, observed_fb()
+(check_preconditions_fb holds):
+    flagged pixels (states other than OK)    750  813  799  799  704  812 1265  949  786
+    filled by the repair                     717  810  757  774  704  776 1032  850  783
+    left unfilled                             33    3   42   25    0   36  233   99    3
+    blobs                                      3    3    3    3    3    3    4    3    3
+    links per transition                         4    4    4    4    5    6    6    4
+    of the 649 points of SEEDS 512 run the whole clip, 34 end UNTRUSTED, 103 LEAVE and none meets an unusable vector; without
+    the repair 267 points end elsewhere; followed by the states as the check left them 288 points end for another reason."""
 import types
 
 import numpy as np
 
 from tests import blob_link_cases as LC
+from tests import consistency_cases as CC
 from tests import photometric_cases as PC
 from tests import repair_cases as RC
+from tests import trajectory_cases as TC
 
 W, H, N_FRAMES = LC.CLIP_W, LC.CLIP_H, 10
 ROWS, COLS = 2, 3
@@ -42,24 +58,53 @@ SMALL = dict(centers=CENTRES[:2], sums=False, histogram=(64, 4.0), camera="trans
 NONE = dict(centers=None, sums=False, histogram=None, camera=None, blobs=None, photometric=None, repair=None)
 
 
+def grid_seeds(w, h, step):
+    """trajectories.grid_seeds(w, h, step) for a whole step: the centres of the step x step cells, row by row, 1/65536 px"""
+    xs = np.arange(step * 32768, (w - 1) * 65536 + 1, step * 65536, dtype=np.int64)
+    ys = np.arange(step * 32768, (h - 1) * 65536 + 1, step * 65536, dtype=np.int64)
+    out = np.empty((len(ys), len(xs), 2), np.int32)
+    out[..., 0], out[..., 1] = xs[None, :], ys[:, None]
+    return out.reshape(-1, 2)
+
+
+FRACTIONS = (1, 32768, 65535)                                        # one quantum past a pixel, half way, one quantum short of the next
+# the centre of every 4x4 cell, then every pairing of FRACTIONS in x and y on nine pixels spread over the frame
+SEEDS = np.concatenate([grid_seeds(W, H, 4),
+                        np.array([[((24 + 36 * i) << 16) + fx, ((18 + 20 * j) << 16) + fy]
+                                  for j, fy in enumerate(FRACTIONS) for i, fx in enumerate(FRACTIONS)], np.int32)])
+SEEDS.setflags(write=False)
+CHECK_FB = dict(alpha=0.01, beta=0.5, keep=(0,))                     # test_gpu_flow_bidir.py's values on this clip
+# the forward-backward check in the photometric one's place, and the trajectories by its states
+ALL_FB = dict(ALL, photometric=None, consistency=CHECK_FB, trajectories=dict(seeds=SEEDS, use_state=True))
+# the photometric check with everything on
+ALL_TRAJ = dict(ALL, trajectories=dict(seeds=SEEDS, use_state=True))
+
+
 def without(spec, stage):
-    """the spec with one stage off: 'photometric', 'repair', 'camera', 'model', 'histogram', 'links' or 'blobs'"""
+    """the spec with one stage off: 'photometric', 'consistency', 'trajectories', 'repair', 'camera', 'model', 'histogram',
+    'links' or 'blobs'.  Without its check a spec's trajectories have no state map to go by: use_state goes off with it."""
     s = dict(spec)
     if stage == "model":
         s.update(centers=None, sums=False)
     elif stage == "links":
         s["blobs"] = dict(spec["blobs"], max_links=0)
     else:
-        assert stage in ("photometric", "repair", "camera", "histogram", "blobs"), stage
+        assert stage in ("photometric", "consistency", "trajectories", "repair", "camera", "histogram", "blobs"), stage
         s[stage] = None
+        if stage in ("photometric", "consistency") and isinstance(s.get("trajectories"), dict):
+            s["trajectories"] = dict(s["trajectories"], use_state=False)
     return s
 
 
 LEAVE_OUT = ("photometric", "repair", "camera", "model", "histogram", "links", "blobs")
+LEAVE_OUT_FB = ("consistency", "trajectories", "repair", "camera", "model", "histogram", "links", "blobs")
 
-# ---- the order.  A step: photo, repair, moves, camera (= camera_fit, camera_sub), cells, counts, hist, blobs, links;
-# blobs_prestate is blobs masked by the states as the check left them, before the repair updated them ----
-DOCUMENTED = ("photo", "repair", "moves", "camera", "cells", "counts", "hist", "blobs", "links")
+# ---- the order.  A step: photo, consist, repair, traj, moves, camera (= camera_fit, camera_sub), cells, counts, hist, blobs,
+# links; blobs_prestate and traj_prestate are blobs masked, and points followed, by the states as the check left them, before
+# the repair updated them.  A step whose stage the spec does not have does nothing. ----
+DOCUMENTED = ("photo", "consist", "repair", "traj", "moves", "camera", "cells", "counts", "hist", "blobs", "links")
+# the chain as it was before the forward-backward check and the trajectories joined it: a spec without them gives the same
+DOCUMENTED_BEFORE = ("photo", "repair", "moves", "camera", "cells", "counts", "hist", "blobs", "links")
 _TAIL = ("cells", "counts", "hist", "blobs", "links")
 # name -> (order, the outputs of the record that must differ from the documented chain's)
 WRONG = {
@@ -73,6 +118,26 @@ WRONG = {
     "blobs-keyed-on-the-unsubtracted-field": (("photo", "repair", "moves", "blobs", "camera", "cells", "counts", "hist", "links"),
                                               ("records",)),
 }
+# the same for a stream with the forward-backward check and the trajectories (ALL_FB); REVERSED: the documented order over the
+# backward fields in the reversed clip's order, the bwd_reversed mix-up of ofc_consist_dev
+WRONG_FB = {
+    "traj-before-the-repair": (("consist", "traj", "repair", "moves", "camera") + _TAIL, ("traj_pos",)),
+    "traj-after-the-camera": (("consist", "repair", "moves", "camera", "traj") + _TAIL, ("traj_pos",)),
+    "traj-by-the-pre-repair-states": (("consist", "repair", "traj_prestate", "moves", "camera") + _TAIL, ("traj_len", "traj_why")),
+    "fb-check-after-the-repair": (("consist", "repair", "consist", "traj", "moves", "camera") + _TAIL, ("consist_counts",)),
+    # the camera is subtracted from the forward field alone, as a stream would do it
+    "fb-check-on-the-residual": (("camera", "consist", "repair", "traj", "moves") + _TAIL, ("consist_counts",)),
+    "fb-blobs-masked-by-the-pre-repair-states": (("consist", "repair", "traj", "moves", "camera", "cells", "counts", "hist",
+                                                  "blobs_prestate", "links"), ("records",)),
+    "backward-fields-in-reverse-order": (DOCUMENTED, ("consist_counts",)),
+}
+REVERSED = ("backward-fields-in-reverse-order",)
+
+
+def compose_wrong_fb(name, frames, fields, back, spec=None, **kw):
+    """the record of the wrong chain WRONG_FB[name] -> (record, the outputs that must differ)"""
+    order, outputs = WRONG_FB[name]
+    return compose(frames, fields, ALL_FB if spec is None else spec, order, back=back[::-1] if name in REVERSED else back, **kw), outputs
 
 
 # ---- the clip ----
@@ -192,28 +257,55 @@ def quantise(tau, kappa):
     return int(round(tau * 256)), int(round(kappa * 256))
 
 
+def quantise_fb(alpha, beta):
+    """consistency.quantise's arithmetic: alpha in 1/65536, beta in px^2 in units of 2^-32"""
+    return int(round(float(alpha) * 65536)), int(round(float(beta) * 2.0 ** 32))
+
+
 OUTPUTS = ("cells", "counts", "sums", "hist", "cam_params", "cam_status", "photo_stats", "repair_counts", "records", "found",
-           "links", "nlinks")
-INTERMEDIATE = ("state_pre", "state", "filled", "moves", "move_field", "labels", "keys", "keys_pre")
-PER_PAIR = ("cells", "counts", "sums", "cam_params", "cam_status", "photo_stats", "repair_counts", "found")
+           "links", "nlinks", "consist_counts", "traj_pos", "traj_len", "traj_why")
+INTERMEDIATE = ("state_pre", "state", "filled", "moves", "move_field", "labels", "keys", "keys_pre", "traj_field")
+PER_PAIR = ("cells", "counts", "sums", "cam_params", "cam_status", "photo_stats", "repair_counts", "found", "consist_counts")
+TRAJ = ("traj_pos", "traj_len", "traj_why")
 
 
-def compose(frames, fields, spec, order=DOCUMENTED, ops=DeviceOps, rows=ROWS, cols=COLS):
+def compose(frames, fields, spec, order=DOCUMENTED, ops=DeviceOps, rows=ROWS, cols=COLS, back=None):
     """frames (n+1,H,W) u8, fields (n,H,W,2) f32 (pair by pair, as FlowEngine(max_batch=1) gives them), spec = FlowStream's
     keyword arguments -> a record with OUTPUTS (None where the stage is off) and the intermediate maps a test may ask
-    about: state_pre (as the check left it), state (as the repair left it), filled, moves, labels, keys, field (as the
-    last stage saw it).  Neither input is written."""
+    about: state_pre (as the check left it), state (as the repair left it), filled, moves, labels, keys, traj_field (as
+    the trajectories saw it), field (as the last stage saw it).  back (n,H,W,2) f32: the field of pair (t+1 -> t) at index
+    t, which a spec with the forward-backward check needs.  No input is written."""
     f = np.array(fields, np.float32)                                 # the chain's field: rewritten, never in place
     r = types.SimpleNamespace(**{k: None for k in OUTPUTS + INTERMEDIATE})
     photo, rep, blob = spec.get("photometric"), spec.get("repair"), spec.get("blobs")
     photo = {} if photo is True else photo
     rep = {} if rep is True else rep
     cam, centres, hist = spec.get("camera"), spec.get("centers"), spec.get("histogram")
+    cons, traj = spec.get("consistency") or None, spec.get("trajectories") or None
+    cons = {} if cons is True else cons
+    traj = {} if traj is True else traj
+    assert photo is None or cons is None, "one check per stream"
+    check = photo if photo is not None else cons                     # the check whose states the later stages go by
+    check_keep = keep_mask(check.get("keep", (0,))) if check is not None else 0
+    if traj is not None:
+        seeds = traj.get("seeds")
+        seeds = grid_seeds(f.shape[2], f.shape[1], traj.get("step", 8)) if seeds is None else np.ascontiguousarray(seeds, np.int32)
+        assert not traj.get("use_state") or check is not None, "use_state needs the state map of a check"
     for step in order:
         if step == "photo" and photo is not None:
             tau_q, kappa_q = quantise(photo.get("tau", 8.0), photo.get("kappa", 0.5))
             r.state_pre, r.photo_stats, _ = PC.reference(frames, f, tau_q, kappa_q)
             r.state = r.state_pre
+        elif step == "consist" and cons is not None:
+            alpha, beta = cons.get("alpha"), cons.get("beta")        # None: consistency.ALPHA and BETA
+            alpha_q, beta_q = quantise_fb(0.01 if alpha is None else alpha, 0.5 if beta is None else beta)
+            r.state_pre, r.consist_counts, _ = CC.reference(f, np.asarray(back, np.float32), alpha_q, beta_q)
+            r.state = r.state_pre
+        elif step in ("traj", "traj_prestate") and traj is not None:
+            st = (r.state_pre if step == "traj_prestate" else r.state) if traj.get("use_state") else None
+            assert st is not None or not traj.get("use_state"), "the trajectories go by a state map no step has made yet"
+            r.traj_field = f
+            r.traj_pos, r.traj_len, r.traj_why = TC.reference(f, seeds, st, check_keep)
         elif step == "repair" and rep is not None:
             f, r.filled, r.repair_counts, st = RC.model(f, r.state, keep_mask(rep.get("keep", (0,))), rep.get("radius", 1),
                                                         rep.get("rounds", 8), rep.get("min_count", 1), rep.get("smooth", False))
@@ -236,9 +328,9 @@ def compose(frames, fields, spec, order=DOCUMENTED, ops=DeviceOps, rows=ROWS, co
             r.hist = np.asarray(ops.hist(f, *hist), np.int64)
         elif step in ("blobs", "blobs_prestate") and blob is not None:
             keys = np.array(ops.keys(f, centres, blob["thr"]), np.uint8)
-            if photo is not None:                                    # a pixel whose state is not kept belongs to no blob
-                r.keys_pre = masked(keys, r.state_pre, keep_mask(photo.get("keep", (0,))))
-                keys = r.keys_pre if step == "blobs_prestate" else masked(keys, r.state, keep_mask(photo.get("keep", (0,))))
+            if check is not None:                                    # a pixel whose state is not kept belongs to no blob
+                r.keys_pre = masked(keys, r.state_pre, check_keep)
+                keys = r.keys_pre if step == "blobs_prestate" else masked(keys, r.state, check_keep)
             r.keys = keys
             r.labels, r.records, r.found = ops.components(keys, f, blob.get("connectivity", 8), blob.get("min_area", 1),
                                                           blob.get("max_blobs", 4096))
@@ -280,7 +372,7 @@ def same_record(got, want, names=OUTPUTS):
 
 def part(rec, a, b):
     """pairs a .. b-1 of a record: the per-pair outputs sliced, the transitions between those pairs; no histogram (a clip's
-    table is a sum, not a slice)"""
+    table is a sum, not a slice) and no trajectories (a clip's points are placed at its own first pair)"""
     out = types.SimpleNamespace(**{k: None for k in OUTPUTS})
     for name in PER_PAIR:
         v = getattr(rec, name)
@@ -316,3 +408,38 @@ def check_preconditions(ref, plain):
     assert (ref.moves != plain.moves).any(), "the repair changes a move word"
     assert (ref.cam_params.view(np.int64) != plain.cam_params.view(np.int64)).any(), "the repair changes a camera parameter bit"
     assert ((ref.keys_pre == 255) & (ref.keys != 255)).any(), "a pixel is background under the pre-repair states and foreground after"
+
+
+def _ends_elsewhere(a, b):
+    """the points that two records leave at different positions when the clip ends: (P,) bool"""
+    return (a.traj_pos[-1] != b.traj_pos[-1]).any(-1)
+
+
+def prestate_trajectories(ref):
+    """ALL_FB's points followed through the field the reference's own were, by the states as the check left them -> (len, why)"""
+    _, length, why = TC.reference(ref.traj_field, SEEDS, ref.state_pre, keep_mask(CHECK_FB["keep"]))
+    return length, why
+
+
+def observed_fb(ref, plain):
+    """the figures the module docstring records for ALL_FB, from the documented reference and the one without the repair"""
+    n = len(ref.consist_counts)
+    moved = _ends_elsewhere(ref, plain)
+    _, why_pre = prestate_trajectories(ref)
+    return dict(flagged=ref.consist_counts[:, 1:].sum(1).tolist(), filled=ref.repair_counts[:, 1].tolist(),
+                unfilled=ref.repair_counts[:, 2].tolist(), points=len(ref.traj_len),
+                why=np.bincount(ref.traj_why, minlength=4).tolist(), whole_clip=int(((ref.traj_why == TC.RAN) & (ref.traj_len == n)).sum()),
+                ends_elsewhere_without_the_repair=int(moved.sum()), why_differs_by_the_pre_repair_states=int((why_pre != ref.traj_why).sum()),
+                blobs=[len(x) for x in ref.records], links=ref.nlinks.tolist())
+
+
+def check_preconditions_fb(ref, plain):
+    """check_preconditions for ALL_FB: the forward-backward check and the repair have work in every pair, the points end
+    for every reason the chain can give them, and both the repaired field and the repaired states change a trajectory"""
+    n = len(ref.consist_counts)
+    assert (ref.consist_counts[:, 1:].sum(1) > 0).all(), "every pair has flagged pixels"
+    assert (ref.repair_counts[:, 1] > 0).all() and ref.repair_counts[:, 2].sum() > 0, "filled in every pair, some unfilled"
+    assert (ref.traj_why == TC.UNTRUSTED).any() and (ref.traj_why == TC.LEAVES).any(), "a point ends UNTRUSTED, another LEAVES"
+    assert ((ref.traj_why == TC.RAN) & (ref.traj_len == n)).any(), "a point runs the whole clip"
+    assert _ends_elsewhere(ref, plain).any(), "the repair changes a point's final position"
+    assert (prestate_trajectories(ref)[1] != ref.traj_why).any(), "a point's why differs between the states before and after the repair"
