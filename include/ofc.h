@@ -1101,6 +1101,66 @@ int ofc_stream_set_traj(ofc_stream_t *s, int64_t P, const int32_t *seeds_host, i
  * the reference. */
 int ofc_stream_read_traj(ofc_stream_t *s, int32_t *pos_host, int32_t *len_host, uint8_t *why_host, int max_pairs);
 
+/* ---- Tracklets: dense trajectories with reseeding.  The block above carries a fixed set of points from the first pair to
+ * the last, so the set thins out and describes only what was visible at frame 0.  Here a pool of tracks is kept on the device:
+ * every frame each grid cell without a live point in it gets a new one, and a track is cut after L steps, so that drift does
+ * not accumulate and all descriptors have one length (the two remaining parts of the dense-trajectories method).  The
+ * reference has no counterpart.
+ * Definition (normative; every output is an integer and does not depend on the order of the work).
+ * Inputs: flow f32 [npair][H][W][2]; optionally state u8 [npair][H][W] with a set `keep`, both as in the block above; `cell`,
+ * the side of a square grid cell in whole px; max_len = L; max_tracks = M.
+ * Grid: cols = ceil(W / cell), rows = ceil(H / cell); cell (cx, cy) has the index cy * cols + cx; the cell of a position is
+ * ((X >> 16) / cell, (Y >> 16) / cell).  The seed of a cell is its centre clamped into the frame:
+ * X0 = min(((cx * cell) << 16) + (cell << 15), (W-1) << 16), Y0 likewise with cy and H.
+ * A track is live while it has not ended and has taken fewer than L steps.  `used` starts at 0.
+ * For frame t = 0 .. npair-1, in this order:
+ * 1. Occupancy.  A cell is occupied iff at least one track that is live before this frame's births has its current position
+ *    in it.
+ * 2. Births.  Take the unoccupied cells in increasing cell index.  With a state map, drop those whose seed's nearest pixel
+ *    (rx, ry of rule 2 above, at (X0, Y0)) has a state s = state[t][ry][rx] with s > 3 or bit s of keep clear: blocked[t]
+ *    counts them.  The cells left are empty[t]; born[t] = min(empty[t], M - used); the first born[t] of them, in cell-index
+ *    order, get the track ids used, used+1, ..: birth = t, pos[0] = the seed, len = 0, why = OFC_TRAJ_RAN.  Then
+ *    used += born[t].
+ * 3. Step.  Every live track, the newborn included, takes exactly the step of the block above (rules 1-4, the same
+ *    quantisation, the same order of reasons) with flow[t] and state[t].  A step that is taken stores the new position in
+ *    pos[len+1] and increments len; a track whose len reaches L then ends with OFC_TRAJ_FULL.  A step that is not taken
+ *    ends the track with that block's reason.
+ * Outputs: pos int32 [L+1][M][2], step-major: pos[k][id] is track id's position after k steps; rows above a track's len, and
+ * all rows of ids >= used, hold (-1, -1) (no inside position is negative).  birth int32 [M]: the frame of the birth, -1 for
+ * unused ids.  len int32 [M]: the steps taken, 0 .. L; 0 for unused ids.  why u8 [M]: OFC_TRAJ_* (OFC_TRAJ_RAN: still live
+ * when the clip ended), 255 for unused ids.  frames int32 [npair][3]: empty, born, blocked of every frame.  used is the sum
+ * of born; born[t] < empty[t] is how a caller sees that the pool ran out, and nothing else changes then.
+ * Limits: W, H as ofc_traj_check; npair 1 .. 65535; cell 1 .. 16384; rows * cols <= 2^24; max_len 1 .. 4096; max_tracks
+ * 1 .. 2^28; keep 0 .. 65535; everything else OFC_EINVAL; then (max_len + 1) * max_tracks >= 2^31 is OFC_EUNSUPPORTED.
+ * Safety: every index is formed from a clamped position, a clamped cell index or a clamped id, whatever the fields hold; no
+ * loop has a data-dependent trip count; no work-group waits for another.
+ * Launches: the clears, then three kernels per frame (count and scan of the empty cells; assignment of the newborn; the
+ * step); the host reads nothing back and does not synchronise between frames. ---- */
+#define OFC_TRAJ_FULL 4                     /* the track took max_len steps */
+#define OFC_TRACKLET_THREADS 256            /* cells, or track ids, a work-group of the three kernels takes */
+#define OFC_TRACKLET_MAX_LEN 4096
+#define OFC_TRACKLET_MAX_TRACKS (1 << 28)
+/* Host only, no device is touched: OFC_OK iff the arguments are inside the limits above.  Every call below decides by it
+ * before anything is allocated or launched.  No counterpart in the reference, as for every call of this block. */
+int ofc_tracklets_check(int W, int H, int npair, int cell, int max_len, int64_t max_tracks, int keep);
+/* flow_dev f32 [npair][H][W][2] (8-byte aligned), state_dev u8 [npair][H][W] or NULL -> pos_dev int32 [max_len+1][max_tracks][2]
+ * (8-byte aligned), birth_dev and len_dev int32 [max_tracks], why_dev u8 [max_tracks], frames_dev int32 [npair][3] (4-byte
+ * aligned).  The outputs must not overlap the inputs or each other.  The call allocates its scratch (the occupancy bitmap,
+ * the counts of the scan, the table of `used` per frame) and frees it on every way out.  Neither input is written.  Returns
+ * when done. */
+int ofc_tracklets_dev(int device, const float *flow_dev, const uint8_t *state_dev, int W, int H, int npair, int cell, int max_len,
+                      int64_t max_tracks, int keep, int32_t *pos_dev, int32_t *birth_dev, int32_t *len_dev, uint8_t *why_dev,
+                      int32_t *frames_dev);
+/* The whole chain on host buffers of the same shapes; state_host may be NULL. */
+int ofc_tracklets(int device, const float *flow_host, const uint8_t *state_host, int W, int H, int npair, int cell, int max_len,
+                  int64_t max_tracks, int keep, int32_t *pos_host, int32_t *birth_host, int32_t *len_host, uint8_t *why_host,
+                  int32_t *frames_host);
+/* Measurement hook: average duration by HIP events over `iters` runs of the whole chain (the clears and every launch), two
+ * warm-up runs before them, on flow_dev without a state map, with outputs and scratch of the hook's own that are allocated
+ * before the timed region and freed when it returns. */
+int ofc_bench_tracklets(int device, const float *flow_dev, int W, int H, int npair, int cell, int max_len, int64_t max_tracks, int iters,
+                        float *ms_per_run);
+
 /* ------------------------------------------------------------------------------------------
  * Downstream consumer of the hue CSVs (findCosineDifferentVectors.py:5-61): cosine similarity between
  * `small` (n_small values) and every window large[i : i+n_small], i = 0 .. n_large-n_small.

@@ -26,6 +26,8 @@ REPAIR_ROUNDS_MAX, REPAIR_NCOUNT, REPAIR_UNFILLED = 254, 3, 255                 
 TRAJ_RAN, TRAJ_UNTRUSTED, TRAJ_LEAVES, TRAJ_INVALID = 0, 1, 2, 3                     # OFC_TRAJ_*: why a point ended
 TRAJ_THREADS, TRAJ_MAX_POINTS = 256, 1 << 28                                         # OFC_TRAJ_THREADS, OFC_TRAJ_MAX_POINTS
 TRAJ_ONE_LAUNCH_POINTS, TRAJ_DENSE_PAIRS = 1 << 19, 16                               # the launch model's two constants
+TRAJ_FULL = 4                                                                        # OFC_TRAJ_FULL: a tracklet that took max_len steps
+TRACKLET_THREADS, TRACKLET_MAX_LEN, TRACKLET_MAX_TRACKS = 256, 4096, 1 << 28         # OFC_TRACKLET_*
 
 
 class OfcError(RuntimeError):
@@ -203,6 +205,10 @@ _PROTOS = {
     "ofc_bench_traj": ([_i, _vp, _i, _i, _i, _vp, _i64, _i, _i, C.POINTER(_f)], _i),
     "ofc_stream_set_traj": ([_vp, _i64, _vp, _i], _i),
     "ofc_stream_read_traj": ([_vp, _vp, _vp, _vp, _i], _i),
+    "ofc_tracklets_check": ([_i, _i, _i, _i, _i, _i64, _i], _i),
+    "ofc_tracklets_dev": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "ofc_tracklets": ([_i, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "ofc_bench_tracklets": ([_i, _vp, _i, _i, _i, _i, _i, _i64, _i, C.POINTER(_f)], _i),
     "ofc_sliding_cosine": ([_i, _vp, _i, _vp, _i, _vp], _i),
     "ofc_synth_frames_dev": ([_i, _vp, _i, _i, _i, _i, _i], _i),
 }

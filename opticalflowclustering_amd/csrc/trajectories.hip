@@ -2,19 +2,18 @@
 // reference has no counterpart: its signature over time was a per-cell mean (drawGridsAndOutputCSV.py), it followed no point.
 //
 // k_traj_steps: one lane per point; a launch covers a chunk of consecutive pairs and the live position stays in registers
-// across it.  The four 8-byte tap gathers and the state byte of a step are issued together before any is used, so a step
-// costs one memory latency on the dependent chain.  Every index -- the state byte's and the taps of ended points included --
+// across it.  The step itself is traj_step.h's, shared with the tracklets (tracklets.hip): the four 8-byte tap gathers and the
+// state byte of a step are issued together before any is used, so a step costs one memory latency on the dependent chain.  Every index -- the state byte's and the taps of ended points included --
 // is formed from the position clamped into the frame, whatever seeds and fields hold, and the trip count is the chunk
 // length.  A step's row of the table is one coalesced 8-byte store per lane (the table is time-major for that), written by
 // ended points too: an ended point stays where it ended.  All arithmetic after the quantisation (fb_check.h) is integer, so
 // the order of the work does not matter.  Between launches the table is the carry: a point is live at step t iff len == t.
 #include "trajectories.h"
+#include "traj_step.h"
 
 namespace ofc {
 
 namespace {
-
-typedef long long i64;
 
 template <bool STATE>
 __global__ __launch_bounds__(TRAJ_THREADS) void k_traj_steps(const float2 *__restrict__ flow, const uint8_t *__restrict__ state, int W,
@@ -25,47 +24,18 @@ __global__ __launch_bounds__(TRAJ_THREADS) void k_traj_steps(const float2 *__res
     const int p = (int)blockIdx.x * TRAJ_THREADS + (int)threadIdx.x;   // P <= 2^28: the grid's lanes stay below 2^28 + 256
     if (p >= P) return;
     const size_t WH = (size_t)W * H;
-    const int xmax = (W - 1) << 16, ymax = (H - 1) << 16;              // W, H <= 16384: below 2^30
     const int2 at = from[p];                                           // the row of step t0
     int X = at.x, Y = at.y, n = len[p], reason = OFC_TRAJ_RAN;
     const bool was_live = n == t0;
     bool live = was_live;
 
     for (int j = 0; j < nstep; j++) {
-        const float2 *F = flow + (size_t)j * WH;
-        // everything that indexes comes from the clamped position; a live point past step 0 is inside, so nothing changes for it
-        const int Xc = min(max(X, 0), xmax), Yc = min(max(Y, 0), ymax);
-        const bool inside = Xc == X && Yc == Y;
-        const int ix = Xc >> 16, iy = Yc >> 16;                        // in [0, W-1], [0, H-1]
-        const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);
-        const int rx = min((Xc + 32768) >> 16, W - 1), ry = min((Yc + 32768) >> 16, H - 1);
-        float2 f0 = make_float2(0.f, 0.f), f1 = f0, f2 = f0, f3 = f0;
-        unsigned sb = 0;
-        if (live) {                                                    // the five loads of the step, none used before all are issued
-            f0 = F[iy * W + ix];
-            f1 = F[iy * W + ix1];
-            f2 = F[iy1 * W + ix];
-            f3 = F[iy1 * W + ix1];
-            if (STATE) sb = state[(size_t)j * WH + (size_t)(ry * W + rx)];
-        }
-        const FbVec q0 = fb_quantise(f0), q1 = fb_quantise(f1), q2 = fb_quantise(f2), q3 = fb_quantise(f3);
-        const i64 fx = Xc & 65535, fy = Yc & 65535;
-        const i64 w0 = (65536 - fx) * (65536 - fy), w1 = fx * (65536 - fy), w2 = (65536 - fx) * fy, w3 = fx * fy;
-        const i64 Sx = w0 * q0.qu + w1 * q1.qu + w2 * q2.qu + w3 * q3.qu;      // |S| <= 2^32 * 2^26
-        const i64 Sy = w0 * q0.qv + w1 * q1.qv + w2 * q2.qv + w3 * q3.qv;
-        const int Xn = Xc + (int)((Sx + (1ll << 31)) >> 32), Yn = Yc + (int)((Sy + (1ll << 31)) >> 32);   // < 2^30 + 2^26
+        const int r = traj_step<STATE>(flow + (size_t)j * WH, STATE ? state + (size_t)j * WH : nullptr, W, H, keep, live, X, Y);
         if (live) {
-            const bool trusted = !STATE || (sb < 4u && ((keep >> sb) & 1u));
-            const bool valid = q0.valid && q1.valid && q2.valid && q3.valid;
-            const bool lands = Xn >= 0 && Xn <= xmax && Yn >= 0 && Yn <= ymax;
-            if (!inside) reason = OFC_TRAJ_LEAVES;
-            else if (!trusted) reason = OFC_TRAJ_UNTRUSTED;
-            else if (!valid) reason = OFC_TRAJ_INVALID;
-            else if (!lands) reason = OFC_TRAJ_LEAVES;
-            if (reason == OFC_TRAJ_RAN) {
-                X = Xn, Y = Yn;
+            if (r == OFC_TRAJ_RAN) {
                 n++;
             } else {
+                reason = r;
                 live = false;
             }
         }

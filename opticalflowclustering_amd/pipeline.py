@@ -274,6 +274,26 @@ class ClipPipeline:
                              state_ptr=state_ptr + start * P if consistent else None, keep=keep, pairs_per_launch=pairs_per_launch,
                              device=self.device)
 
+    def tracklets(self, cell=8, length=15, max_tracks=None, start=0, pairs=None, consistent=False, keep=(0,)):
+        """dense trajectories with reseeding on the resident field (trajectories.follow_dense; ofc_tracklets_dev) ->
+        trajectories.Tracklets: every frame each cell x cell grid cell without a live track gets a new one, and a track is
+        cut after `length` steps.  The clip starts at pair `start` and has `pairs` pairs (None: to the end): a sub-range is
+        a pointer offset into the field.  max_tracks None: trajectories.default_max_tracks for the range.  consistent=True
+        and the refusals as trajectories().  Rank-local: this rank's pairs."""
+        from . import trajectories as tr
+        if self._compensated:
+            raise ValueError("tracklets() after compensate_camera() would follow the residual, which does not say where a "
+                             "pixel lands: call it before compensate_camera()")
+        start = int(start)
+        n = self.n_pairs - start if pairs is None else int(pairs)
+        if not (0 <= start < self.n_pairs and 1 <= n <= self.n_pairs - start):
+            raise ValueError(f"start = {start}, pairs = {pairs!r}: a range of the clip's {self.n_pairs} pairs")
+        state_ptr = self._state_ptr("tracklets(consistent=True)") if consistent else None
+        self.sync()
+        P = self.W * self.H
+        return tr.follow_dense_dev(self.flows.ptr + start * P * 8, self.W, self.H, n, cell=cell, length=length, max_tracks=max_tracks,
+                                   state_ptr=state_ptr + start * P if consistent else None, keep=keep, device=self.device)
+
     def filled_host(self):
         """host copy of repair()'s map: (n,H,W) u8, 0 for a source, g for a pixel filled in round g, 255 for one never filled"""
         if self.filled is None:
