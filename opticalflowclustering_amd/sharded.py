@@ -1,4 +1,4 @@
-"""Host-driven sharded Lloyd: the same control flow as libofc's in-library driver (lloyd_api.cpp ==
+"""Host-driven sharded Lloyd: the same control flow as libofc's in-library driver (lloyd_fit.cpp ==
 sklearn's _kmeans_single_lloyd, _kmeans.py:624-752), but with the per-iteration exchange handed to a
 caller-supplied collective, so that shards can be combined by ANY transport -- torch.distributed with
 gloo across nodes, or RCCL.  Every rank holds a contiguous shard of the rows (frame-sharded (u,v) vectors)

@@ -82,7 +82,7 @@ def main():
     C0 = np.array([[0.0, 0.0], [1.0, 1.0], [500.0, 500.0]])
     run("reloc_f64_k3", B[:4096].astype(np.float64), C0, S)
     # several empty clusters in one iteration (sklearn hands far points to empty clusters in argpartition order; the C
-    # oracle, lloyd_api.cpp and sharded.py go farthest-first: these pin that the two agree): 2 and 3 far-away centres
+    # oracle, lloyd_fit.cpp and sharded.py go farthest-first: these pin that the two agree): 2 and 3 far-away centres
     C0 = np.array([[0.0, 0.0], [1.0, 1.0], [500.0, 500.0], [-400.0, 300.0]])
     run("reloc2_f64_k4", B[:4096].astype(np.float64), C0, S)
     C0 = np.array([[0.5, -0.5], [-1.0, 0.3], [600.0, 0.0], [0.0, -700.0], [-300.0, -300.0], [1.5, 1.5]])

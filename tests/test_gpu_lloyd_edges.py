@@ -328,6 +328,34 @@ def test_farthest_with_every_sample_excluded(L):
     assert (d2, idx, lab) == (-1.0, -1, -1)
 
 
+def test_farthest_twins_in_two_work_groups_and_the_fit_that_relocates_one(L):
+    """4096 f32 samples (4 work-groups) in two tight clusters, and the same far point at indices 100 and 3000, which lie in
+    different work-groups.  The third initial centre is where nobody is nearest: the farthest pick must name index 100, and
+    the fit relocates the empty cluster onto the far point (sklearn: iteration 0 moves it there, iteration 1 gives it both
+    twins, whose mean is the point itself)."""
+    from opticalflowclustering_amd.cluster import KMeans
+    N, far = 4096, np.array([5.0, 50.0], np.float32)
+    rng = np.random.default_rng(12)
+    X = (np.array([[0.0, 0.0], [10.0, 0.0]])[np.arange(N) % 2] + 0.01 * rng.standard_normal((N, 2))).astype(np.float32)
+    X[[100, 3000]] = far
+    C0 = np.array([[0.0, 0.1], [10.0, 0.1], [5.0, -1000.0]])
+    mean = mean_of(X)
+    sh = Shard(L, X)
+    run_step(L, sh, mean, C0 - mean)
+    lab = sh.labels()
+    assert lab[100] == lab[3000] and 2 not in lab
+    d2, idx, xc, l = sh.s.farthest(mean, C0 - mean, [])
+    assert np.array_equal(idx, 100) and l == lab[100] and np.array_equal(xc, far.astype(np.float64) - mean)
+    d2b, idx, _, _ = sh.s.farthest(mean, C0 - mean, [100])
+    assert np.array_equal(idx, 3000) and d2b == d2
+    km = KMeans(n_clusters=3, init=C0).fit(X)
+    cen, olab, inertia, n_iter = O.kmeans_fit(X, C0)
+    assert km.n_iter_ == n_iter and np.array_equal(km.labels_, olab)
+    assert np.array_equal(np.flatnonzero(km.labels_ == 2), [100, 3000])
+    assert np.abs(km.cluster_centers_ - cen).max() <= 1e-9 and np.abs(km.cluster_centers_[2] - far).max() <= 1e-9
+    assert abs(km.inertia_ - inertia) <= 1e-10 * inertia
+
+
 # ------------------------------------------------------------------------------------------------ k-means++ step
 def run_kpp(L, X, mean, cand, closest):
     from opticalflowclustering_amd.cluster import _DT

@@ -1,4 +1,4 @@
-"""Lloyd's k-means with sample weights on the MI355X (lloyd_weighted.hip, the weighted paths of lloyd_api.cpp, cluster.py,
+"""Lloyd's k-means with sample weights on the MI355X (lloyd_weighted.hip, the weighted paths of lloyd_fit.cpp, cluster.py,
 sharded.py, pipeline.py) against scikit-learn 1.7.2's goldens (tests/golden/make_lloyd_weighted_goldens.py) and the float64
 numpy model of tests/lloyd_weighted_cases.py, which tests/test_lloyd_weighted_host.py pins to those goldens.
 

@@ -32,7 +32,7 @@ def src(name):
 
 # ------------------------------------------------------------------------------------------------ the model itself
 def test_model_constants_are_the_kernels():
-    tiles, kern, api = src("lloyd_tiles.hip"), src("lloyd_kernels.hip"), src("lloyd_api.cpp")
+    tiles, kern, api = src("lloyd_tiles.hip"), src("lloyd_kernels.hip"), src("lloyd_fit.cpp")
     assert "wmax < -1e-12 * mag" in tiles
     assert "pure >= 0.45 * tested" in tiles
     assert "if (frac < 0.3)" in kern and "frac >= 0.45 ? LLOYD_TILES_PRUNED : LLOYD_TILES_FULL" in kern
