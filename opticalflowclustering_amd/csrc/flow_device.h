@@ -1,8 +1,21 @@
-// flow_device.h -- device-side pieces of the Farneback iteration shared by flow_kernels.hip (what ships) and
-// flow_experiments.hip (the opt-in round-2 experiments): the per-pixel update-matrices arithmetic and the column march's
-// step height.  Included inside namespace-free translation units; everything lives in namespace ofc.
+// flow_device.h -- device-side pieces shared by the hand-written gfx950 kernels of the Farneback pyramid (SURVEY.md 2.2
+// K2-K6): flow_pyramid.hip (level images), flow_polyexp.hip (expansion), flow_solve.hip (staged K4 / K5 / K6) and
+// flow_iter.hip (fused iteration) hold what ships, flow_experiments.hip the opt-in experiments.  Here: the bilinear tap and
+// border helpers, the per-pixel update-matrices arithmetic and the column march's step height.  Included inside
+// namespace-free translation units; everything lives in namespace ofc.
+//
+// All kernels are batched over images / frame pairs through blockIdx.z so that even the coarse
+// pyramid levels (240x135 at 1080p) fill the 256 CUs.  Layouts in HBM:
+//   frames  [n][H0][W0] u8            pyramid image I [n][h][w] f32
+//   R       [n][h][w][5] f32 pixel-interleaved (5 coefficients = 20 contiguous bytes: the bilinear gather of the
+//                                      flow iteration reads 40-byte runs; producer stores stay fully coalesced)
+//   M       [p][5][h][w] f32 planar   flow [p][h][w][2] f32 (the ABI layout of cv2's output)
+//
+// Arithmetic follows the oracle (oracle/farneback_ref.c == SURVEY.md App. A) statement by statement.
+// Kernels that are purely memory bound keep FP contraction OFF so that they reproduce the oracle
+// bit for bit; polyexp and the box filter use FMAs / exact f64 sums (differences ~1e-7 relative).
 #pragma once
-#include "lloyd_common.h"
+#include "lloyd_common.h"     // launch_reduce_records (fixed-order sum of records)
 
 #include <algorithm>
 #include <climits>
@@ -10,6 +23,39 @@
 namespace ofc {
 
 constexpr int BS_ROWS = 4;      // rows per step of the column march (k_box_solve, k_flow_iter)
+
+// ------------------------------------------------------------------------------------------------
+// bilinear tap helpers (imgproc resize INTER_LINEAR)
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void lin_tap_x(int dx, double scale, int sw, int &s0, float &a)
+{
+#pragma clang fp contract(off)
+    float fx = (float)((dx + 0.5) * scale - 0.5);
+    int sx = (int)floorf(fx);
+    fx -= (float)sx;
+    if (sx < 0) { fx = 0.f; sx = 0; }
+    if (sx >= sw - 1) { fx = 0.f; sx = sw - 1; }
+    s0 = sx;
+    a = fx;
+}
+
+__device__ __forceinline__ void lin_tap_y(int dy, double scale, int sh, int &s0, int &s1, float &b)
+{
+#pragma clang fp contract(off)
+    float fy = (float)((dy + 0.5) * scale - 0.5);
+    int sy = (int)floorf(fy);
+    fy -= (float)sy;
+    s0 = min(max(sy, 0), sh - 1);
+    s1 = min(max(sy + 1, 0), sh - 1);
+    b = fy;
+}
+
+__device__ __forceinline__ int reflect101(int p, int len)
+{
+    if (len == 1) return 0;
+    while (p < 0 || p >= len) p = p < 0 ? -p : 2 * (len - 1) - p;
+    return p;
+}
 
 // ------------------------------------------------------------------------------------------------
 // K4  update matrices: bilinear warp-sample of R1 at x+flow, G/h products, border attenuation.

@@ -3,6 +3,7 @@
 // Declared in include/ofc.h (which cites the reference call each entry point replaces).
 #include "color_common.h"
 #include "fb_check.h"
+#include "flow_host.h"
 #include "host_util.h"
 #include "lloyd_common.h"
 
@@ -424,6 +425,34 @@ static int flow_batch_check(const ofc_flow *f, bool pointers_ok, int n_frames)
     OFC_REQUIRE(f && pointers_ok, "null pointer");
     OFC_REQUIRE(n_frames >= 2 && n_frames - 1 <= f->max_batch, "n_frames-1 = %d pairs not in [1, max_batch=%d]",
                 n_frames - 1, f->max_batch);
+    return OFC_OK;
+}
+
+// The walk ofc_flow_create runs over an engine's levels before it allocates anything: every limit the launches of
+// flow_run apply that follows from the frame size and the parameters alone, asked of the same functions the launches
+// ask (level_image_check over level_image_plan, flow_iter_check), coarsest level first as flow_run visits them.  A refusal
+// names the level and the limit.  (Engine buffers are hipMalloc'ed, so the level images see dword-aligned frames; a level
+// that takes a decimation path when aligned also fits the general path's limits, so the answer does not depend on that.)
+static int flow_levels_check(int W, int H, const ofc_fb_params &p, const LevelGeom *geom, int levels, bool fused, bool fuse_level0)
+{
+    for (int k = levels; k >= 0; k--) {
+        const LevelGeom &g = geom[k];
+        int rc = OFC_OK;
+        if (!(k == 0 && fuse_level0 && polyexp_u8_ok(W, H, g))) rc = level_image_check(W, H, g, true);
+        if (rc == OFC_OK && fused) rc = flow_iter_check(g.w, g.h, p.winsize);
+        if (rc == OFC_OK) continue;
+        const std::string why = ofc_last_error();
+        if (g.ksize > 31) {
+            int ok = k;         // the deepest level whose blur fits: the `levels` this pyr_scale allows at this size
+            while (ok > 0 && geom[ok].ksize > 31) ok--;
+            set_error("pyramid level %d (%dx%d, sigma %.3g) of %dx%d at pyr_scale %g: %s; levels <= %d is supported with this "
+                      "pyr_scale (a level may shrink the frame by less than 13.6x)", k, g.w, g.h, g.sigma, W, H, p.pyr_scale,
+                      why.c_str(), ok);
+        } else {
+            set_error("pyramid level %d (%dx%d) of %dx%d at pyr_scale %g: %s", k, g.w, g.h, W, H, p.pyr_scale, why.c_str());
+        }
+        return rc;
+    }
     return OFC_OK;
 }
 

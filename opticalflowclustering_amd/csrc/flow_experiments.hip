@@ -2,8 +2,9 @@
 // what was measured ("Round 2"): k_flow_iter2 (two iterations per launch, OFC_FLOW_FUSE2) and
 // k_flow_iter_w3 (3 waves per SIMD, OFC_FLOW_W3); and round 3's k_flow_iter_p (gathers software-pipelined across steps, ring
 // partly in LDS, OFC_FLOW_PIPE).  All are SLOWER than k_flow_iter on MI355X and never run unless their switch is set;
-// flow_kernels.hip holds what ships.
+// flow_iter.hip holds what ships.
 #include "flow_device.h"
+#include "flow_host.h"
 
 namespace ofc {
 

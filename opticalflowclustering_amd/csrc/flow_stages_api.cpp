@@ -1,5 +1,6 @@
 // flow_stages_api.cpp -- C ABI of libofc.so: the single stages of the Farneback flow on host buffers (parity-test hooks), the
 // launch-geometry exports and the bench hooks of single kernels.  The engine itself is in flow_engine.cpp.
+#include "flow_host.h"
 #include "host_util.h"
 
 #include <algorithm>

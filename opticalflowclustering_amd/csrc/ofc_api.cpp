@@ -2,7 +2,7 @@
 // constants every flow file shares, and the memory plumbing (ofc_version .. ofc_device_sync).  The flow engine is in
 // flow_engine.cpp, its single-stage and bench hooks in flow_stages_api.cpp.
 // Declared in include/ofc.h (which cites the reference call each entry point replaces).
-#include "ofc_common.h"
+#include "flow_host.h"
 
 #include <cfloat>
 #include <cmath>

@@ -2,7 +2,7 @@
 float64) share, and the inputs both build from them.  numpy only at import: the float64 restatement pulls scipy in when it
 is called, which the GPU module never does.
 
-Tile geometry restated from csrc/flow_kernels.hip: k_flow_iter<M, UPS> and k_box_solve<M> (M = winsize / 2) both give a
+Tile geometry restated from csrc/flow_iter.hip and csrc/flow_solve.hip: k_flow_iter<M, UPS> and k_box_solve<M> (M = winsize / 2) both give a
 256-thread work-group 256 - 2M = 256 - (winsize - 1) output columns, so the seams between work-groups fall on multiples of
 T = 257 - winsize; flow_iter_rows / box_default_rows cut the rows into strips that are multiples of 16 (box: of 4)."""
 import json
@@ -146,7 +146,7 @@ def recorded_stage_distances():
 
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. stage level: level images at other pyramid scales.  Geometry and launch path restated from ofc_api.cpp
-#    (level_geometry, pyramid_levels) and flow_kernels.hip (level_image_plan), python's round() being cvRound's half-to-even
+#    (level_geometry, pyramid_levels) and flow_pyramid.hip (level_image_plan), python's round() being cvRound's half-to-even
 # ---------------------------------------------------------------------------------------------------------------------
 def pyramid_levels(W, H, pyr_scale, levels):
     k, scale = 0, 1.0

@@ -4,8 +4,8 @@ with the labels and branch targets that give the loops their shape, and between 
 stores, LDS instructions and everything else.  What it is for: seeing which outstanding memory operations a wait at a loop
 head covers ("Waits that reach into the stores").
 
-    hipcc <the Makefile's CXXFLAGS> -S --cuda-device-only flow_kernels.hip -o flow_kernels.s
-    python tools/waitcnt_listing.py flow_kernels.s 'k_flow_iterILi7ELi0ELb0ELb0E'
+    hipcc <the Makefile's CXXFLAGS> -S --cuda-device-only flow_iter.hip -o flow_iter.s
+    python tools/waitcnt_listing.py flow_iter.s 'k_flow_iterILi7ELi0ELb0ELb0E'
 
 The second argument is a substring of the kernel's (mangled) symbol; the assembly is the compiler's -S output.  The kernel's
 register and occupancy figures (.vgpr_count, .vgpr_spill_count, .private_segment_fixed_size of its metadata record) are printed
